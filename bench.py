@@ -17,10 +17,13 @@ the same communicator, the RCCL unique id travels over a local TCP socket (qcat_
 --gpus N without a launcher environment starts the N ranks itself and fails if the node has fewer
 than N devices.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel's ALGORITHMIC bytes
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the line;
+--dump-outputs DIR also writes what the last timed step computed (DIR/<name>.npy, see dump_outputs()),
+and --full adds the legs that take work of their own: host_inclusive (+ from_fastq), cpu_baseline,
+parity and dp_cells.  `roofline` prices the dominant kernel's ALGORITHMIC bytes
 (150 B per scanned read end + 24 B result record) against the 8 TB/s HBM peak,
 with the kernel's average duration measured by HIP events on the library's own stream;
-`cpu_baseline` times the CPU oracle (a port, not the reference: parasail is absent) on a bounded
+`cpu_baseline` (--full) times the CPU oracle (a port, not the reference: parasail is absent) on a bounded
 sample of the same reads on the host cores of this box (rank 0, at every N: the other ranks wait at
 the final barrier).  `valu_issue` is the VALU view of the DP phases from COUNTERS, not from a model:
 SQ_INSTS_VALU per launch (the newest profiles/r0N_pmc.json, rocprofv3 --pmc on this workload; replayed with a staleness guard) x 2 issue cycles /
@@ -64,6 +67,7 @@ WORKLOADS = {
     "api1": ("epi2me", None, native.ENDS_BOTH, 3, 2, 324, 2000),
 }
 HBM_PEAK_GBS = 8000.0
+DUMP_SAMPLE_READS = 500000          # --dump-outputs: 11 float64 arrays of this many reads, 44 MB
 
 
 def usable_cores():
@@ -109,11 +113,19 @@ def parse():
                     help="CPU time of the oracle sample (cpu_baseline + parity); short by default so that the GPU work is not a\n"
                          "sliver of the run the driver's gpu_busy samples see")
     ap.add_argument("--batch", type=int, default=4000, help="api4000: reads per detect_barcode_batch call (cli.py:500)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: host_inclusive (+ from_fastq), cpu_baseline, parity, dp_cells; "
+                         "api4000: called_fraction; api1: the kit-auto leg and the single-read vs batch check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64): the count vector and every "
+                         "record field of a fixed, seeded sample of %d reads (rank 0's shard)" % DUMP_SAMPLE_READS)
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
     if a.workload is None:
         a.workload = "config3" if a.gpus == 1 else "config4"
+    if a.dump_outputs and a.workload in ("api4000", "api1"):
+        ap.error("--dump-outputs: the resident workloads only (api4000 / api1 return Python dicts)")
     if a.reads is None:
         a.reads = WORKLOADS[a.workload][6]
     if a.seed is None:
@@ -196,6 +208,7 @@ def main():
 
     for _ in range(a.warmup):
         step()
+    # (the headline has always been timed with the per-phase events on: they feed roofline / valu_issue at no extra run)
     hip.check(lib.qcat_ctx_set_timing(ctx.handle, 1))
     kernel_ms = {}
     names = (C.c_char_p * 16)()
@@ -214,15 +227,19 @@ def main():
     if comm is not None:
         elapsed = comm.allreduce([elapsed], native.REDUCE_MAX)[0]
 
-    # ---- results of the last step: parity spot check + counts -------------------------------
-    recs = np.zeros(a.reads, dtype=native.RESULT_DTYPE)
-    hip.check(lib.qcat_ctx_fetch_results(ctx.handle, recs.ctypes.data, a.reads))
+    # ---- results of the last step: counts (+ the records for --dump-outputs and the parity legs of --full) ----------------
+    recs = None
+    if a.full or a.dump_outputs:
+        recs = np.zeros(a.reads, dtype=native.RESULT_DTYPE)
+        hip.check(lib.qcat_ctx_fetch_results(ctx.handle, recs.ctypes.data, a.reads))
     total_counts = np.zeros(n_buckets, dtype=np.int64)          # after the all-reduce: the global histogram
     hip.check(lib.qcat_ctx_fetch_counts(ctx.handle, total_counts.ctypes.data, n_buckets))
     n_barcode_buckets = n_buckets - len(desc.kit_names) - 2      # [barcodes.., none][kits.., none][skipped]
     counts_total = int(total_counts[:n_barcode_buckets].sum())
     if counts_total != world * a.reads:
         sys.exit("bench.py: the count vector holds %d reads, expected %d" % (counts_total, world * a.reads))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, recs, total_counts, a.seed)
 
     if rank == 0:
         value = world * a.reads * a.steps / elapsed
@@ -270,7 +287,7 @@ def main():
         if "rccl_counts_allreduce" in avg:
             out["count_allreduce_ms"] = round(avg["rccl_counts_allreduce"], 4)
         out["valu_issue"] = valu_issue(a, avg)
-    if not a.no_host_inclusive:
+    if a.full and not a.no_host_inclusive:
         # PCIe-inclusive rate of the host-buffer entry point (never `value`): download the shard (at N > 1 its
         # first 2 M reads: N ranks x 9.5 GB of pageable host copies are not needed to see the rate), then time
         # qcat_scan_batch (upload + scan + 24 B/read download) three times, keep the fastest; at N > 1 all
@@ -280,7 +297,7 @@ def main():
             out["host_inclusive"] = hi
     if rank == 0:
         # ---- CPU baseline + parity on a bounded sample of rank 0's shard (every N) --------------
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             cpu_legs(a, out, lib, kit, sp, desc, det, cfg, mode, recs)
         print(json.dumps(out))
         sys.stdout.flush()
@@ -288,6 +305,19 @@ def main():
     if comm is not None:
         comm.barrier()
         comm.close()
+
+
+def dump_outputs(dirname, recs, counts, seed):
+    """--dump-outputs: the last timed step's count vector (every bucket) and, for a fixed sample of reads drawn with `seed`,
+    the read indices and every field of their result records, each as DIR/<name>.npy in float64 (the integers are exact)."""
+    os.makedirs(dirname, exist_ok=True)
+    n = len(recs)
+    idx = np.sort(np.random.RandomState(seed).choice(n, size=DUMP_SAMPLE_READS, replace=False)) if n > DUMP_SAMPLE_READS else np.arange(n)
+    sample = recs[idx]
+    arrays = {"counts": counts, "read_index": idx}
+    arrays.update((name, sample[name]) for name in recs.dtype.names)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def cgroup_cpu_stat():
@@ -668,8 +698,8 @@ def api4000(a, hip, lib):
         reads.append(buf[:ln].tobytes().decode("ascii"))
     batches = [reads[i:i + a.batch] for i in range(0, len(reads), a.batch)]
     quals = [[None] * len(b) for b in batches]
-    for b, q in list(zip(batches, quals))[:max(1, a.warmup)]:
-        det.detect_barcode_batch(b, q, cfg)
+    for i in range(max(1, a.warmup)):                       # (a step is one batch call, the batches taken in turn)
+        det.detect_barcode_batch(batches[i % len(batches)], quals[i % len(batches)], cfg)
     split = {"pack_reads_s": 0.0, "native_call_s": 0.0, "dicts_s": 0.0}
     ctx = det._context()
     orig_scan_auto, orig_pack, orig_dicts = ctx.scan_auto, native.pack_reads, det._records_to_dicts
@@ -689,34 +719,33 @@ def api4000(a, hip, lib):
     native.read_views = timed("pack_reads_s", orig_views)     # (the str objects' buffers handed over as they are: csrc/pyglue.c)
     det._records_to_dicts = timed("dicts_s", orig_dicts)
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        for b, q in zip(batches, quals):
-            res = det.detect_barcode_batch(b, q, cfg)
+    for i in range(a.steps):
+        det.detect_barcode_batch(batches[i % len(batches)], quals[i % len(batches)], cfg)
     elapsed = time.perf_counter() - t0
     ctx.scan_auto, native.pack_reads, det._records_to_dicts = orig_scan_auto, orig_pack, orig_dicts
     native.read_views, ctx.scan_auto_views = orig_views, orig_scan_views
-    # the sanity figure `called_fraction` comes from one more pass outside the timed region (counting 4000 dicts in Python is
-    # 0.25 ms per call: the bench's own bookkeeping, not the call's)
-    called = 0
-    for b, q in zip(batches, quals):
-        called += sum(1 for r in det.detect_barcode_batch(b, q, cfg) if r["barcode"] is not None)
-    called *= a.steps
-    n_calls = a.steps * len(batches)
-    total = a.steps * len(reads)
+    n_calls = a.steps
+    total = sum(len(batches[i % len(batches)]) for i in range(a.steps))
     out = {"metric": "reads/sec demultiplexed", "value": round(total / elapsed, 1), "unit": "reads/s", "n_gpus": 1,
            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / n_calls * 1e3, 4), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "int16 / bit planes", "data": "synthetic",
            "config": {"workload": "api4000: detect_barcode_batch on %d-read batches (qcat/cli.py:500-513), kit auto "
                                   "(%d templates), results as Python dicts; %d synthetic PBC096 reads as Python strings; "
-                                  "a step here is one batch call" % (a.batch, len(det.layouts), len(reads)),
+                                  "a step here is one batch call, the batches taken in turn" % (a.batch, len(det.layouts), len(reads)),
                       "batch": a.batch, "calls": n_calls, "reads_total": total},
            "split_ms_per_call": {k[:-2] + "_ms": round(v / n_calls * 1e3, 4) for k, v in split.items()},
            "python_helper": "qcat_amd/_pyglue.so (read pointers + dicts in C)" if native._pyglue is not None else "none (pure-Python conversions)",
            "other_python_ms_per_call": round((elapsed - sum(split.values())) / n_calls * 1e3, 4),
-           "called_fraction": round(called / float(total), 4),
            "roofline": None, "cpu_baseline": None,
            "note": "host-driven call shape: the GPU kernels of a 4000-read batch take a fraction of the call; "
                    "roofline / cpu_baseline belong to the resident workloads (default run)"}
+    if a.full:
+        # the sanity figure `called_fraction` comes from one more pass outside the timed region (counting 4000 dicts in Python is
+        # 0.25 ms per call: the bench's own bookkeeping, not the call's)
+        called = 0
+        for b, q in zip(batches, quals):
+            called += sum(1 for r in det.detect_barcode_batch(b, q, cfg) if r["barcode"] is not None)
+        out["called_fraction"] = round(called / float(len(reads)), 4)
     print(json.dumps(out))
     sys.stdout.flush()
 
@@ -736,7 +765,8 @@ def api1(a, hip, lib):
         ln = lib.qcat_synth_read(gkit.handle, C.byref(sp), i, buf.ctypes.data, buf.size)
         reads.append(buf[:ln].tobytes().decode("ascii"))
     legs = {}
-    for name, det in (("named_kit", gen), ("kit_auto", scanner.factory(mode="epi2me", kit=None))):
+    dets = [("named_kit", gen)] + ([("kit_auto", scanner.factory(mode="epi2me", kit=None))] if a.full else [])
+    for name, det in dets:
         for r in reads[:max(8, a.warmup)]:
             det.detect_barcode(r, None, cfg)
         split = {"pack_reads_s": 0.0, "native_call_s": 0.0, "dicts_s": 0.0}
@@ -756,17 +786,17 @@ def api1(a, hip, lib):
         det._records_to_dicts = timed("dicts_s", orig_dicts)
         t0 = time.perf_counter()
         called = 0
-        for _ in range(a.steps):
-            for r in reads:
-                called += det.detect_barcode(r, None, cfg)["barcode"] is not None
+        for i in range(a.steps):                     # (a step is one call, the reads taken in turn)
+            called += det.detect_barcode(reads[i % len(reads)], None, cfg)["barcode"] is not None
         elapsed = time.perf_counter() - t0
         ctx.scan, native.pack_reads, det._records_to_dicts = orig_scan, orig_pack, orig_dicts
-        n_calls = a.steps * len(reads)
-        # the same reads through one batch call: the single-read calls must give the same results
-        batch = det._run(reads, det.layouts, cfg)
-        single = [det.detect_barcode(r, None, cfg) for r in reads[:200]]
-        if any(s != b for s, b in zip(single, batch[:200])):
-            sys.exit("bench.py: detect_barcode on single reads and on the batch disagree")
+        n_calls = a.steps
+        if a.full:
+            # the same reads through one batch call: the single-read calls must give the same results
+            batch = det._run(reads, det.layouts, cfg)
+            single = [det.detect_barcode(r, None, cfg) for r in reads[:200]]
+            if any(s != b for s, b in zip(single, batch[:200])):
+                sys.exit("bench.py: detect_barcode on single reads and on the batch disagree")
         legs[name] = {"ms_per_call": round(elapsed / n_calls * 1e3, 4), "calls_per_s": round(n_calls / elapsed, 1), "templates": len(det.layouts),
                       "split_ms_per_call": {k[:-2] + "_ms": round(v / n_calls * 1e3, 4) for k, v in split.items()},
                       "other_python_ms_per_call": round((elapsed - sum(split.values())) / n_calls * 1e3, 4),
@@ -775,8 +805,9 @@ def api1(a, hip, lib):
            "steps": a.steps, "warmup": a.warmup, "ms_per_step": legs["named_kit"]["ms_per_call"], "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "int16 / bit planes", "data": "synthetic",
            "config": {"workload": "api1: detect_barcode on ONE read per call (qcat/test/test_barcode.py:84, cli.py:504-509), results as "
-                                  "Python dicts; %d synthetic PBC096 reads as Python strings; value = the named-kit leg; a step here is "
-                                  "one call" % len(reads), "calls": a.steps * len(reads)},
+                                  "Python dicts; %d synthetic PBC096 reads as Python strings; value = the named-kit leg (--full: the "
+                                  "kit-auto leg beside it); a step here is one call, the reads taken in turn" % len(reads),
+                      "calls": a.steps},
            "legs": legs, "roofline": None, "cpu_baseline": None,
            "note": "host-driven call shape: one read is two windows -- the kernels are latency, not throughput; roofline / cpu_baseline "
                    "belong to the resident workloads (default run)"}

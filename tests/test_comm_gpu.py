@@ -129,7 +129,7 @@ def test_bench_under_a_launcher_environment_with_one_rank():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(parallel.free_port()))
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--reads", "100000", "--cpu-seconds", "1"],
+                        "--reads", "100000", "--cpu-seconds", "1", "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
@@ -155,7 +155,7 @@ def test_rehearsal_of_eight_ranks_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     t0 = time.time()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "rehearse_gpus8.py"), "--launch", "--gpus", "8",
-                        "--reads", "1000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"],
+                        "--reads", "1000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().strip().splitlines() if l.startswith("{")]

@@ -12,7 +12,7 @@ bash tools/profile.sh ${tag}_dual dual --steps 5 --warmup 1 > $out/prof_dual.log
 bash tools/profile.sh ${tag}_middle middle --steps 5 --warmup 1 > $out/prof_middle.log 2>&1
 cd $GRAFT_REPO_ROOT
 for wl in config3 config2 dual dual96 config4 middle api4000 api1; do
-  timeout 900 python bench.py --workload $wl > $out/bench_$wl.json 2> $out/bench_$wl.err
+  timeout 900 python bench.py --full --workload $wl > $out/bench_$wl.json 2> $out/bench_$wl.err
   python -c "
 import json; d=json.load(open('$out/bench_$wl.json')); print('$wl', d['value'], d['ms_per_step'], (d.get('roofline') or {}).get('frac'), d.get('parity'))" 2>&1 | cut -c1-300
 done

@@ -18,4 +18,4 @@ PY
   done
 done
 QCAT_HIP_BS_TRACE=1 QCAT_HIP_BS_PIPE=1 timeout 300 python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-host-inclusive > $out/trace_pipe1.json 2> $out/trace_pipe1.txt
-QCAT_HIP_BS_PIPE=1 timeout 300 python bench.py --steps 3 --warmup 1 --no-host-inclusive --cpu-seconds 5 > $out/pipe1_parity.json 2>$out/pipe1_parity.err; tail -c 600 $out/pipe1_parity.json
+QCAT_HIP_BS_PIPE=1 timeout 300 python bench.py --full --steps 3 --warmup 1 --no-host-inclusive --cpu-seconds 5 > $out/pipe1_parity.json 2>$out/pipe1_parity.err; tail -c 600 $out/pipe1_parity.json

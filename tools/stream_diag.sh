@@ -20,8 +20,8 @@ f = d["host_inclusive"]["from_fastq"]
 print(sys.argv[2], f["value"], f["stream"], "whole", f["whole_file"]["value"])
 PY
 }
-timeout 600 python bench.py --steps 3 --warmup 1 > $out/bench_default.json 2> $out/bench_default.err; show $out/bench_default.json default
-timeout 600 python bench.py --steps 3 --warmup 1 --reads 1000000 > $out/bench_1m.json 2> $out/bench_1m.err; show $out/bench_1m.json reads_1m
-timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_nocpu.json 2> $out/bench_nocpu.err; show $out/bench_nocpu.json no_cpu_baseline
-QCAT_HIP_PIPELINE_TRACE=1 timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_trace.json 2> $out/bench_trace.err; show $out/bench_trace.json traced
+timeout 600 python bench.py --full --steps 3 --warmup 1 > $out/bench_default.json 2> $out/bench_default.err; show $out/bench_default.json default
+timeout 600 python bench.py --full --steps 3 --warmup 1 --reads 1000000 > $out/bench_1m.json 2> $out/bench_1m.err; show $out/bench_1m.json reads_1m
+timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_nocpu.json 2> $out/bench_nocpu.err; show $out/bench_nocpu.json no_cpu_baseline
+QCAT_HIP_PIPELINE_TRACE=1 timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_trace.json 2> $out/bench_trace.err; show $out/bench_trace.json traced
 grep "split of\|populate\|CPU seconds" $out/bench_trace.err | tail -12
