@@ -235,7 +235,8 @@ int kit_prepare(const qcat_kit_desc* d, HostKit* hk, std::string* err) {
                 q.bs_post = bs_post_of(q.bs_rev ? q.uplen : q.downlen, q.tlen, q.bs_pre);
                 q.bs_short_min = (q.bs_post > 0 && q.hot_len != d->max_align_length) ? std::max(1, q.hot_len - BS_PAD_ROWS) : q.hot_len;
                 const int own = q.tlen - q.bs_pre - q.bs_post;
-                bool plain = own >= BS_C_MIN && own <= BS_C_MAX && q.tlen <= 64 && q.n <= 128 && q.hot_len <= 150;
+                // (BS_MAX_TARGET: a target of 64 columns read without an error scores 64, one more than the counters' seven planes hold)
+                bool plain = own >= BS_C_MIN && own <= BS_C_MAX && q.tlen <= BS_MAX_TARGET && q.n <= 128 && q.hot_len <= 150;
                 for (size_t x = 0; x < (size_t)q.n * q.tlen && plain; ++x) plain = hk->codes[q.tgt_off + x] <= 3;
                 if (plain) {
                     q.bs_off = (int32_t)hk->ids.size();

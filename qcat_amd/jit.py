@@ -14,6 +14,9 @@ missing) and hands the code object to the library (``qcat_kit_attach_code``).
     QCAT_AMD_JIT=0           never generate code
     QCAT_AMD_JIT_CACHE=dir   where code objects are kept (default ~/.cache/qcat_amd); every cached
                              object is stored with its SHA-256 and verified before it is loaded
+    QCAT_AMD_JIT_NO_ABS=1    no bit-sliced adapter plans in the generated unit
+    QCAT_AMD_JIT_NO_BS=1     no bit-sliced barcode kernels with the kit's letters compiled in (the bulk of the compile
+                             time of a big set); big batches run the letters-from-memory form instead
 
 When no compiler is available the kit stays on the table kernels and a warning says so (once).
 There is no reference counterpart (the reference has one code path); results are identical on
@@ -278,7 +281,9 @@ def generate(descriptor, skip_templates=(), skip_groups=()):
                          "qj_bc_%d(qk::StaticArgs a) { qk::barcode_static_body<qk::QSGJ_%d>(a); }\n" % (2 if quad_list else 4, g, g))
             grp_flags[g] = 1
             # bit-sliced rows with the letters compiled in (kernels_bitslice.inc): case = barcode index
-            shape = _bs_shape(len(up), len(dn), m) if len(targets) <= 128 else None
+            # (QCAT_AMD_JIT_NO_BS: no such kernel -- a second of compile time per barcode; the kit's bit-sliced units then take
+            # their letters from memory)
+            shape = _bs_shape(len(up), len(dn), m) if len(targets) <= 128 and os.environ.get("QCAT_AMD_JIT_NO_BS") is None else None
             if shape:
                 rev, pre, own, post = shape
                 s1, s0 = _bs_shared_words(targets[0], rev, pre)
@@ -307,6 +312,7 @@ BS_C_MIN, BS_C_MAX = 20, 48          # kit.h
 
 
 BS_POSTS = (11, 8, 7, 6, 4)          # kit.h: bs_post_of
+BS_MAX_TARGET = 63                   # kit.h: a 64-column target read without an error scores 64, beyond the counters' planes
 
 
 def _bs_shape(uplen, downlen, m):
@@ -318,7 +324,7 @@ def _bs_shape(uplen, downlen, m):
     pre = 11 if lead >= 11 else (8 if lead >= 8 else (4 if lead >= 4 else 0))
     post = next((q for q in BS_POSTS if q <= trail and m - pre - q >= BS_C_MIN), 0)
     own = m - pre - post
-    if not (BS_C_MIN <= own <= BS_C_MAX and m <= 64):
+    if not (BS_C_MIN <= own <= BS_C_MAX and m <= BS_MAX_TARGET):
         return None
     return rev, pre, own, post
 

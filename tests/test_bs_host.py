@@ -69,3 +69,30 @@ def test_bit_sliced_barcode_arithmetic_equals_the_oracle_dp(host_check, tmp_path
     assert p.returncode == 0, out[-3000:] + p.stderr.decode()[-3000:]
     rows = [l for l in out.splitlines() if l.startswith("family")]
     assert len(rows) == len(lines) and all(l.endswith("split: 0 mismatches, unsplit: 0 mismatches, front-padded: 0 mismatches") for l in rows), out[-3000:]
+
+
+def test_the_longest_target_the_counters_hold(host_check, tmp_path):
+    """a score counter holds H + 64 in [0, 127] (bs_core.h) and a target read without an error scores its length: 63 columns
+    are the most the bit-sliced kernels can take (kit.h BS_MAX_TARGET; kit_prepare.inc, jit._bs_shape and the generator's
+    bs_shape leave a 64-column set on the binary16 kernels).  Found by the kit-geometry sweep: custom kits with targets of 64
+    columns lost every perfect read on the bit-sliced path (64 wraps).  63 columns in both directions, split and unsplit,
+    against the oracle's DP -- the batches of the host check hold error-free regions"""
+    import gen_static_kernels as g
+    from qcat_amd import jit
+    rng = random.Random(63)
+    lines = []
+    for uplen, dnlen in ((11, 4), (6, 11), (11, 11)):
+        assert g.bs_shape(uplen, dnlen, 64) is None and jit._bs_shape(uplen, dnlen, 64) is None
+        shape = g.bs_shape(uplen, dnlen, 63)
+        assert shape is not None and shape == jit._bs_shape(uplen, dnlen, 63)
+        up = "".join(rng.choice("ACGT") for _ in range(uplen))
+        dn = "".join(rng.choice("ACGT") for _ in range(dnlen))
+        targets = [up + "".join(rng.choice("ACGT") for _ in range(63 - uplen - dnlen)) + dn for _ in range(6)]
+        lines.append("%d %d %d %s" % (shape[0], shape[1], shape[3], " ".join(targets)))
+    fam = tmp_path / "families.txt"
+    fam.write_text("\n".join(lines) + "\n")
+    p = subprocess.run([host_check, str(fam), "63", "3"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    out = p.stdout.decode()
+    assert p.returncode == 0, out[-3000:] + p.stderr.decode()[-3000:]
+    rows = [l for l in out.splitlines() if l.startswith("family")]
+    assert len(rows) == 3 and all(l.endswith("split: 0 mismatches, unsplit: 0 mismatches, front-padded: 0 mismatches") for l in rows), out[-3000:]

@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import geometry_cases
 import oracle_lib
 import synth
 from qcat_amd import native, scanner
@@ -32,6 +33,10 @@ def test_generated_source_is_in_sync_with_the_kit_bundle():
     assert open(gen.OUT).read() == text, "run python tools/gen_static_kernels.py"
     assert open(gen.BS_OUT).read() == bs_text, "run python tools/gen_static_kernels.py"
     assert n_kernels >= 16 and n_targets >= 600 and n_templates >= 14
+    # no shipped target family is longer than the bit-sliced kernels' score counters hold (kit.h BS_MAX_TARGET, restated in the
+    # generator and in qcat_amd/jit.py): the limit leaves the generated files as they were
+    from qcat_amd import jit
+    assert gen.BS_MAX_TARGET == jit.BS_MAX_TARGET == 63 and max(m for _, _, m in gen.collect()[0]) < 63
 
 
 @pytest.mark.parametrize("mode", ["epi2me", "dual"])
@@ -271,15 +276,7 @@ def test_packed_detect_middle_with_custom_scoring(match, mismatch, gap):
     assert np.array_equal(cnt, o_cnt)
 
 
-def _subset_kit(tmp_path, picks):
-    import yaml
-    lay = scanner.factory(kit="PBC096").layouts[0]
-    bcs = lay.get_barcode_set(0)
-    rows = [{"name": "barcode%02d" % (i + 1), "id": i + 1, "sequence": bcs[p].sequence, "fwd_strand": True} for i, p in enumerate(picks)]
-    data = {"kit": "SUBSET", "auto_detect": False, "description": "subset", "sequence": lay.sequence, "trim_offset": 0,
-            "barcode_set_1": rows, "barcode_set_2": []}
-    (tmp_path / "s.yml").write_text(yaml.safe_dump(data))
-    return scanner.factory(kit="SUBSET", kit_folder=str(tmp_path))
+_subset_kit = geometry_cases.subset_kit
 
 
 def test_any_subset_of_a_known_barcode_family_is_static(tmp_path):
@@ -288,6 +285,22 @@ def test_any_subset_of_a_known_barcode_family_is_static(tmp_path):
     det = _subset_kit(tmp_path, [95, 2, 49, 10, 9])
     info = native.NativeKit(det.descriptor()).describe()
     assert info["n_static_templates"] == 1 and info["n_static_groups"] == 1
+    # ... and every partial, permuted and reversed set the GPU sweep runs (tests/test_kit_geometry_gpu.py): the chains AND the
+    # built-in bit-sliced kernel of the family (bitslice_groups: groups with a bit-sliced form, in the high half those with
+    # the letters compiled in)
+    for name, picks in sorted(geometry_cases.pbc096_subsets().items()):
+        info = native.NativeKit(geometry_cases.descriptor(geometry_cases.subset_layouts(picks))).describe()
+        assert info["packed"] == 1 and info["n_static_templates"] == 1 and info["n_static_groups"] == 1, (name, info)
+        assert info["bitslice_groups"] == 0x10001, (name, info)
+    for n2 in (49, 95, 96):
+        info = native.NativeKit(geometry_cases.descriptor(geometry_cases.dual_subset_layouts(n2), mode="dual")).describe()
+        assert info["n_static_templates"] == 2 and info["n_static_groups"] == info["n_groups"] == 4, (n2, info)
+        assert info["bitslice_groups"] == 0x40004, (n2, info)
+    # a set that names a target twice binds no chain (two kit indices cannot share one chain's score register): table kernels
+    seq, _ = geometry_cases.pbc096()
+    for name, bcs in sorted(geometry_cases.tie_sets().items()):
+        info = native.NativeKit(geometry_cases.descriptor([geometry_cases.layout("REPEATS", seq, bcs)]), jit=False).describe()
+        assert info["packed"] == 1 and info["n_static_groups"] == 0 and info["bitslice_groups"] == 0x1, (name, info)
 
 
 @gpu

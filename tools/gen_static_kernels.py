@@ -25,6 +25,7 @@ QUAD_MIN_TARGETS = 48       # families this large also get four-target chains (t
 BS_MIN_TARGETS = 12         # families this large get bit-sliced row loops with the letters compiled in (kernels_bitslice.inc)
 BS_C_MIN, BS_C_MAX = 20, 48 # kit.h
 BS_POSTS = (11, 8, 7, 6, 4) # trailing columns the reversed DP takes (kit_prepare.inc, the instantiations of kernels_bitslice.inc)
+BS_MAX_TARGET = 63          # kit.h: a score counter holds up to 63 and a target read without an error scores its length
 BS_PARTS = 6                # translation units the bit-sliced static-letter kernels are split over (__graft_entry__.build)
 BS_OUT = os.path.join(ROOT, "qcat_amd", "csrc", "bs_static_generated.inc")
 CODE = {"A": 0, "T": 1, "G": 2, "C": 3}
@@ -67,7 +68,7 @@ def bs_shape(uplen, downlen, m):
     pre = 11 if lead >= 11 else (8 if lead >= 8 else (4 if lead >= 4 else 0))
     post = next((q for q in BS_POSTS if q <= trail and m - pre - q >= BS_C_MIN), 0)
     own = m - pre - post
-    if not (BS_C_MIN <= own <= BS_C_MAX and m <= 64):
+    if not (BS_C_MIN <= own <= BS_C_MAX and m <= BS_MAX_TARGET):
         return None
     return rev, pre, own, post
 
