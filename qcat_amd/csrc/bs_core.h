@@ -247,5 +247,220 @@ BS_FN void bs_finish(u32 (&rowbest)[BS_NB], u32 (&r)[BS_NB], const u32 (&f)[BS_N
     bs_max(rowbest, r);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The END of a barcode without a score counter per column (round 7).  After the row loops a barcode holds the C last-row
+// codes  code_j = dh(L,j) + 1  of its own columns and the deficit D of the line in front of the trailing context, and needs
+//       raw = max( H(L,c) + D,  max_{1<=j<=c} H(L,j),  cmax )                                  (c = P + C, see above).
+// Stepping a 7-plane counter and taking a 7-plane maximum once per column (bs_step + bs_max: 41 instructions a column) is
+// replaced by two cheaper walks over the codes:
+//  * the row maximum as a DEFICIT.  E_j = max(rowbest0, max_{k<=j} H(L,k)) - H(L,j), rowbest0 = the maximum over the shared
+//    columns.  E_j = max(E_{j-1} + 1 - code_j, 0) -- the recurrence of bs_deficit -- and the row maximum is H(L,c) + E_c.
+//    Range: the maximum is attained in a column k in [1, j] and dh >= -1, so 0 <= E_j <= j - k <= j - 1 <= 62 for targets of
+//    up to BS_MAX_TARGET = 63 columns: BS_NE = 6 planes, and E + 1 - min(code, E + 1) <= 63 inside the update.
+//    E_P = rowbest0 - H(L,P) depends on the shared columns only (bs_last_row_start, once per unit).  A set without shared
+//    columns has no column 0 candidate (H(L,0) = 0 is not a cell of the last row): its first own column sets E_1 = 0.
+//  * H(L,c) as ONE sum.  H(L,c) + 64 = [H(L,P) + 64 - C] + sum_j code_j.  The bracket ("base") comes from the producer of the
+//    shared columns: in [64 - P - C, 64 + P - C], within [1, 127] for P + C <= 63, seven planes.  The C low bits of the
+//    codes and the C high bits are counted by carry-save trees (bs_popcount: a full adder is one parity and one majority
+//    instruction; the two lowest planes of base ride along as the trees' spare carry inputs), at most 49 ones each for the
+//    C <= 48 the kernels instantiate: six planes.  low + 2 high + 4 (base >> 2) is taken modulo 128; the value itself,
+//    H(L,c) + 64, lies in [64 - c, 64 + c], within [1, 127].
+// Then  raw + 64 = max( H(L,c) + 64 + max(D, E_c), cmax ):  H(L,c) + D = max_i G(i) <= M <= 63 and H(L,c) + E_c = the row
+// maximum <= c <= 63, so the sum stays within seven planes.
+// ---------------------------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BS_UNROLL _Pragma("unroll")
+#define BS_PHASE_END() __builtin_amdgcn_sched_barrier(0)        // the scheduler keeps the phases of bs_last_row apart: what one needs is not live in the others
+#else
+#define BS_UNROLL
+#define BS_PHASE_END() ((void)0)
+#endif
+
+constexpr int BS_NE = 6;                      // planes of the last row's deficit E in [0, 62]
+
+// E' = max(E + 1 - a, 0) = E + 1 - m,  m = min(a, E + 1)  (a = dh + 1 of the last row's next column): 16 instructions
+BS_FN void bs_rowmax_deficit(u32 (&e)[BS_NE], u32 a1, u32 a0) {
+    const u32 hi = QB3(e[2], e[3], e[4], x | y | z);
+    const u32 big = QB3(hi, e[5], e[1], x | y | z);                                           // E >= 2: m = a
+    const u32 m1 = QB3(a1, big, e[0], x & (y | z));                                            // a >= 2 and E >= 1
+    const u32 t = QB3(a0, big, e[0], (x & (y | ~z)) | (~x & ~y & ~z));                         // a = 3: E != 1; a = 2: E = 0
+    const u32 m0 = bs_bfi(a1, t, a0);
+    // E += 1 - m: in two's complement (.., m1, m1, ~m0)
+    u32 c = QB3(e[0], m0, m0, x & ~y);
+    e[0] = QB3(e[0], m0, m0, ~(x ^ y));
+    BS_UNROLL
+    for (int k = 1; k < BS_NE; ++k) {
+        const u32 s = QB3(e[k], m1, c, x ^ y ^ z);
+        if (k + 1 < BS_NE) c = QB3(e[k], m1, c, (x & y) | (x & z) | (y & z));
+        e[k] = s;
+    }
+}
+
+constexpr int bs_planes_of(int n) { int b = 0; while ((1 << b) <= n) ++b; return b; }         // planes that hold 0 .. n
+
+// out (bs_planes_of(N) planes) = how many of the N words in[] have the bit set, per bit: a tree of full adders -- the last
+// word is the carry input of the adder that joins the counts of the two halves
+template <int N>
+BS_FN void bs_popcount(const u32* in, u32* out) {
+    if constexpr (N == 1) {
+        out[0] = in[0];
+    } else if constexpr (N == 2) {
+        out[0] = in[0] ^ in[1];
+        out[1] = in[0] & in[1];
+    } else {
+        constexpr int NL = N / 2, NR = N - 1 - NL, WL = bs_planes_of(NL), WR = bs_planes_of(NR), W = bs_planes_of(N);
+        static_assert(NL >= NR && NR >= 1 && W <= WL + 1, "the left count is the wider one");
+        u32 l[WL], r[WR];
+        bs_popcount<NL>(in, l);
+        bs_popcount<NR>(in + NL, r);
+        u32 c = in[N - 1];
+        BS_UNROLL
+        for (int k = 0; k < WL; ++k) {
+            const bool more = k + 1 < W;                                                      // (the count fits W planes: no carry beyond)
+            if (k < WR) {
+                out[k] = QB3(l[k], r[k], c, x ^ y ^ z);
+                if (more) c = QB3(l[k], r[k], c, (x & y) | (x & z) | (y & z));
+            } else {
+                out[k] = l[k] ^ c;
+                if (more) c = l[k] & c;
+            }
+        }
+        if (W > WL) out[WL] = c;
+    }
+}
+
+// acc += y << SH modulo 2^BS_NB.  AW: planes of acc that can be set on entry, W: planes of y -- absent planes cost nothing
+template <int AW, int W, int SH>
+BS_FN void bs_add_planes(u32 (&acc)[BS_NB], const u32* y) {
+    u32 c = 0u;
+    bool carry = false;
+    BS_UNROLL
+    for (int k = SH; k < BS_NB; ++k) {
+        const bool ha = k < AW, hy = k < SH + W, last = k + 1 == BS_NB;
+        if (ha && hy && carry) {
+            const u32 s = QB3(acc[k], y[k - SH], c, x ^ y ^ z);
+            if (!last) c = QB3(acc[k], y[k - SH], c, (x & y) | (x & z) | (y & z));
+            acc[k] = s;
+        } else if (ha && (hy || carry)) {
+            const u32 o = hy ? y[k - SH] : c;
+            const u32 s = acc[k] ^ o;
+            if (!last) c = acc[k] & o;
+            acc[k] = s;
+            carry = true;
+        } else if (hy && carry) {
+            acc[k] = y[k - SH] ^ c;
+            if (!last) c = y[k - SH] & c;
+        } else if (hy || carry) {
+            acc[k] = hy ? y[k - SH] : c;
+            carry = false;
+        }
+    }
+}
+
+// what the producer of the shared columns leaves for bs_last_row: base = H(L,P) + 64 - C and E_P = rowbest0 - H(L,P), from the
+// last-row codes (h1 h0) of the P shared columns and the number C of own columns.  P = 0: base = 64 - C, E = 0.
+BS_FN void bs_last_row_start(u32 (&base)[BS_NB], u32 (&e)[BS_NE], const u32* h1, const u32* h0, int P, int C) {
+    u32 best[BS_NB];
+    BS_UNROLL
+    for (int q = 0; q < BS_NB; ++q) { base[q] = ((BS_OFF - C) >> q) & 1 ? 0xFFFFFFFFu : 0u; best[q] = 0u; }
+    BS_UNROLL
+    for (int j = 0; j < P; ++j) { bs_step(base, h1[j], h0[j]); bs_max(best, base); }         // (base >= 64 - C - P >= 1 > the start of best)
+    u32 bw = 0u;
+    BS_UNROLL
+    for (int q = 0; q < BS_NE; ++q) {
+        e[q] = P > 0 ? (u32)QB3(best[q], base[q], bw, x ^ y ^ z) : 0u;
+        bw = QB3(best[q], base[q], bw, (~x & y) | (~(x ^ y) & z));
+    }
+}
+
+// the end of a barcode: raw + 64 = max(H(L,c) + 64 + max(D, E_c), cmax) from the C last-row codes (h1 h0), the deficit d and
+// the unit's tail (header comment above): tail(q) = plane q of base, tail(BS_NB + q) = plane q of E_P -- both as
+// bs_last_row_start leaves them -- and tail(2 BS_NB + q) = plane q of cmax = max_j R(L,j) + 64; each is fetched where it is
+// needed.  SHARED: the set has shared columns.
+template <int C, bool SHARED, class TAIL>
+BS_FN void bs_last_row(u32 (&raw)[BS_NB], const u32 (&h1)[C], const u32 (&h0)[C], TAIL tail, const u32 (&d)[BS_ND]) {
+    static_assert(BS_ND == BS_NB && BS_NE == BS_NB - 1, "the maximum of D and E below");
+    constexpr int WP = bs_planes_of(C + 1);
+    static_assert(C >= 2 && WP + 1 <= BS_NB, "the two counts of code bits fit the score planes");
+    u32 e[BS_NE];
+    BS_UNROLL
+    for (int q = 0; q < BS_NE; ++q) e[q] = tail(BS_NB + q);
+    BS_UNROLL
+    for (int j = SHARED ? 0 : 1; j < C; ++j) bs_rowmax_deficit(e, h1[j], h0[j]);
+    BS_PHASE_END();
+    u32 base[BS_NB];
+    BS_UNROLL
+    for (int q = 0; q < BS_NB; ++q) base[q] = tail(q);
+    u32 lo[C + 1], hi[C + 1], cl[WP], ch[WP];
+    BS_UNROLL
+    for (int j = 0; j < C; ++j) { lo[j] = h0[j]; hi[j] = h1[j]; }
+    lo[C] = base[0]; hi[C] = base[1];
+    bs_popcount<C + 1>(lo, cl);
+    bs_popcount<C + 1>(hi, ch);
+    BS_UNROLL
+    for (int q = 0; q < BS_NB; ++q) raw[q] = q < WP ? cl[q] : 0u;
+    bs_add_planes<WP, WP, 1>(raw, ch);
+    bs_add_planes<(WP + 2 < BS_NB ? WP + 2 : BS_NB), BS_NB - 2, 2>(raw, &base[2]);            // raw = H(L,c) + 64
+    BS_PHASE_END();
+    // max(D, E): E has no top plane
+    u32 gt = QB3(e[BS_NE - 1], d[BS_NE - 1], d[BS_NE], x & ~y & ~z);
+    u32 eq = QB3(e[BS_NE - 1], d[BS_NE - 1], d[BS_NE], ~(x ^ y) & ~z);
+    BS_UNROLL
+    for (int k = BS_NE - 2; k >= 0; --k) {
+        gt |= QB3(eq, e[k], d[k], x & y & ~z);
+        if (k) eq = QB3(eq, e[k], d[k], x & ~(y ^ z));
+    }
+    u32 c = 0u;
+    BS_UNROLL
+    for (int q = 0; q < BS_NB; ++q) {
+        const u32 m = q < BS_NE ? bs_bfi(gt, e[q], d[q]) : d[q];
+        const u32 s = q ? (u32)QB3(raw[q], m, c, x ^ y ^ z) : raw[q] ^ m;
+        if (q + 1 < BS_NB) c = q ? (u32)QB3(raw[q], m, c, (x & y) | (x & z) | (y & z)) : raw[q] & m;
+        raw[q] = s;
+    }
+    u32 cmax[BS_NB];
+    BS_UNROLL
+    for (int q = 0; q < BS_NB; ++q) cmax[q] = tail(2 * BS_NB + q);
+    bs_max(raw, cmax);
+}
+
+// ---------------------------------------------------------------------------------------------
+// 32 x 32 bit matrix in registers, transposed in place: out[b] bit k = in[k] bit b (five butterfly stages of 16 word pairs,
+// a shift and a bit-field insert per word)
+BS_FN void bs_transpose32(u32 (&a)[32]) {
+    BS_UNROLL
+    for (int s = 0; s < 5; ++s) {
+        const int j = 16 >> s;
+        const u32 m = s == 0 ? 0x0000FFFFu : (s == 1 ? 0x00FF00FFu : (s == 2 ? 0x0F0F0F0Fu : (s == 3 ? 0x33333333u : 0x55555555u)));
+        BS_UNROLL
+        for (int k = 0; k < 32; ++k) {
+            if (k & j) continue;
+            const u32 lo = a[k], hi = a[k + j];
+            a[k] = bs_bfi(m, lo, hi << j);
+            a[k + j] = bs_bfi(m, lo >> j, hi);
+        }
+    }
+}
+
+// The hand-over of a wave's best (raw + 64, barcode index) planes as one key per alignment: the key of kernels_packed.inc,
+//       barcode_key(raw, b) = (raw + 32768) << 16 | (1023 - b),
+// is itself a bit pattern of the planes.  With v = raw + 64 in [0, 127]: raw + 32768 = 0x7FC0 + v = (v & 63) | (v6 ? 0x8000 :
+// 0x7FC0) -- bits 0..5 are v's, bits 6..14 are ~v6, bit 15 is v6 -- and 1023 - b = ~b in ten bits for b < 128.  So the 32 rows
+// below, transposed, are the 32 keys of a lane: no bit is picked out of a plane word one alignment at a time.
+BS_FN void bs_keys32(u32 (&key)[32], const u32 (&bestv)[BS_NB], const u32 (&besti)[BS_NB]) {
+    BS_UNROLL
+    for (int q = 0; q < 32; ++q) {
+        u32 w;
+        if (q < BS_NB) w = ~besti[q];
+        else if (q < 10) w = 0xFFFFFFFFu;
+        else if (q < 16) w = 0u;
+        else if (q < 16 + BS_NB - 1) w = bestv[q - 16];
+        else if (q < 31) w = ~bestv[BS_NB - 1];
+        else w = bestv[BS_NB - 1];
+        key[q] = w;
+    }
+    bs_transpose32(key);
+}
+
 }  // namespace qk
 #endif

@@ -198,8 +198,9 @@ k_bs_plan(const DevKit* __restrict__ k, const JobTables* __restrict__ jt, BsNch 
     for (int q = 0; q < 8; ++q) bp->cursor[q][0] = 0;
 }
 
-// shared columns of a super-tile: dv at column PP of every row into the LDS rows, the last-row counters after PP columns
-// into the tail.  The rows depend on each other.  Two forms:
+// shared columns of a super-tile: dv at column PP of every row into the LDS rows, and what the last row of a barcode with
+// `cown` own columns starts from after PP columns -- H(L,PP) + 64 - cown and the row maximum's deficit E (bs_core.h:
+// bs_last_row_start) -- into the tail.  The rows depend on each other.  Two forms:
 //  * SOLO = false (every wave of the workgroup has barcodes to do): the workgroup waits for the phase, so the waves that
 //    take part each compute all rows and store their share.  Round 5: ONE wave per SIMD walks the leading context and one
 //    the trailing context (bs_trailing_columns) -- two waves per SIMD run at the full issue rate, so the second context's
@@ -213,7 +214,7 @@ k_bs_plan(const DevKit* __restrict__ k, const JobTables* __restrict__ jt, BsNch 
 // row i < npad -- their dh planes go back to the boundary state after the row (bs_core.h: bs_hold)
 template <int PP, bool SOLO, class NEQ>
 __device__ __forceinline__ void bs_shared_columns(uint4* __restrict__ s_rows, u32* __restrict__ s_tail, int L, int lane, int wave, NEQ neq, u32* ready,
-                                                  const u32* __restrict__ hold, int npad) {
+                                                  const u32* __restrict__ hold, int npad, int cown) {
     u32 h1[PP > 0 ? PP : 1], h0[PP > 0 ? PP : 1];
 #pragma unroll
     for (int j = 0; j < PP; ++j) { h1[j] = 0u; h0[j] = 0xFFFFFFFFu; }
@@ -235,13 +236,12 @@ __device__ __forceinline__ void bs_shared_columns(uint4* __restrict__ s_rows, u3
         }
     }
     if (SOLO || wave == 0) {
-        u32 r[BS_NB], rowbest[BS_NB];
+        u32 base[BS_NB], e[BS_NE];
+        bs_last_row_start(base, e, h1, h0, PP, cown);
 #pragma unroll
-        for (int q = 0; q < BS_NB; ++q) { r[q] = (BS_OFF >> q) & 1 ? 0xFFFFFFFFu : 0u; rowbest[q] = 0u; }
+        for (int q = 0; q < BS_NB; ++q) s_tail[q * 64 + lane] = base[q];
 #pragma unroll
-        for (int j = 0; j < PP; ++j) { bs_step(r, h1[j], h0[j]); bs_max(rowbest, r); }
-#pragma unroll
-        for (int q = 0; q < BS_NB; ++q) { s_tail[q * 64 + lane] = r[q]; s_tail[(BS_NB + q) * 64 + lane] = rowbest[q]; }
+        for (int q = 0; q < BS_NE; ++q) s_tail[(BS_NB + q) * 64 + lane] = e[q];
         if (SOLO) __hip_atomic_store(ready, (u32)(L + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 }
@@ -307,11 +307,11 @@ __device__ __forceinline__ void bs_wait_rows(const u32* ready, int need) {
 // ... letters from memory: bit j of (l1, l0) = letter of column j (two more instructions per cell, both with a scalar source)
 template <int PP, bool SOLO>
 __device__ __forceinline__ void bs_shared_columns_dynamic(uint4* __restrict__ s_rows, u32* __restrict__ s_tail, int L, int lane, int wave,
-                                                          u32 l1, u32 l0, u32* ready, const u32* hold, int npad) {
+                                                          u32 l1, u32 l0, u32* ready, const u32* hold, int npad, int cown) {
     bs_shared_columns<PP, SOLO>(s_rows, s_tail, L, lane, wave, [&](int j, u32 c1, u32 c0) {
         const u32 L1 = (u32)-(int)((l1 >> j) & 1u), L0 = (u32)-(int)((l0 >> j) & 1u);
         return bs_neq(c1, c0, L1, L0);
-    }, ready, hold, npad);
+    }, ready, hold, npad, cown);
 }
 template <int QQ, bool SOLO>
 __device__ __forceinline__ void bs_trailing_columns_dynamic(const uint4* __restrict__ s_rows, uint2* __restrict__ rp, u32* __restrict__ s_tail, int L, int lane,
@@ -325,10 +325,10 @@ __device__ __forceinline__ void bs_trailing_columns_dynamic(const uint4* __restr
 // ... letters as template constants (generated code: the two contexts of a target family)
 template <int PP, unsigned S1, unsigned S0, bool SOLO>
 __device__ __forceinline__ void bs_shared_columns_static(uint4* __restrict__ s_rows, u32* __restrict__ s_tail, int L, int lane, int wave, u32* ready,
-                                                         const u32* hold, int npad) {
+                                                         const u32* hold, int npad, int cown) {
     bs_shared_columns<PP, SOLO>(s_rows, s_tail, L, lane, wave, [&](int j, u32 c1, u32 c0) {
         return bs_neq_letter((int)((S1 >> j) & 1u) * 2 + (int)((S0 >> j) & 1u), c1, c0);
-    }, ready, hold, npad);
+    }, ready, hold, npad, cown);
 }
 template <int QQ, unsigned T1, unsigned T0, bool SOLO>
 __device__ __forceinline__ void bs_trailing_columns_static(const uint4* __restrict__ s_rows, uint2* __restrict__ rp, u32* __restrict__ s_tail, int L, int lane,
@@ -351,11 +351,12 @@ __device__ __forceinline__ void bs_setprio(int p) {                    // (the p
 // (i + 1, j - 1) do not depend on each other, so the in-order VALU always has a second dependency chain to issue from.
 // NEQ(j, c1, c0): mismatch mask of own column j against a row's letter planes.  The last own cell of a row feeds the
 // deficit of G(i) = H(i, c) + R(L - i, Q) together with the row's plane pair of the trailing columns (bs_deficit_split).
-// what a barcode's row loop is given (one struct: the generated kernels pass it through)
+// what a barcode's row loop is given (one struct: the generated kernels pass it through).  SHARED (a template parameter of
+// the row loops: the generated kernels know it, the letters-from-memory kernels switch on it once per barcode): the set has
+// shared columns -- dv + 1 left of the first own column comes from the rows
 struct BsRowArgs {
     const uint4* rows;                          // LDS rows of the unit
     int L, lane;
-    bool shared;                                // the set has shared columns: dv + 1 left of the first own column comes from the rows
     const u32* ready;                           // a SOLO unit's progress word (bs_shared_columns); null: the planes are complete
     int nact;                                   // waves of this wave's SIMD that walk barcodes in this unit (1..4): the priority rotation's period
     const uint2* rp;                            // global: per row and lane dv + 1 of the trailing columns' last column (bs_trailing_columns)
@@ -364,12 +365,12 @@ struct BsRowArgs {
     const u32* hold;                            // and who (LDS, [row][lane]); 0: none
 };
 
-template <int C, bool PAIRS, class NEQ>
+template <int C, bool PAIRS, bool SHARED, class NEQ>
 __device__ __forceinline__ void bs_rows(const BsRowArgs& ra, NEQ neq, u32 (&h1)[C], u32 (&h0)[C], u32 (&f)[BS_ND]) {
     const uint4* __restrict__ s_rows = ra.rows;
     const uint2* __restrict__ rp = ra.rp + ra.lane;
     const int L = ra.L, lane = ra.lane;
-    const bool shared = ra.shared;
+    constexpr bool shared = SHARED;
     const u32* ready = ra.ready;
     int i = 0;
     bs_wait_rows(ra.ready_r, 1);
@@ -451,10 +452,10 @@ __device__ __forceinline__ void bs_rows(const BsRowArgs& ra, NEQ neq, u32 (&h1)[
 }
 
 // ... letters from memory: bit j of (l1w, l0w) = letter of own column j
-template <int C>
+template <int C, bool SHARED>
 __device__ __forceinline__ void bs_rows_dynamic(const BsRowArgs& ra, unsigned long long l1w, unsigned long long l0w,
                                                 u32 (&h1)[C], u32 (&h0)[C], u32 (&f)[BS_ND]) {
-    bs_rows<C, true>(ra, [&](int j, u32 c1, u32 c0) {
+    bs_rows<C, true, SHARED>(ra, [&](int j, u32 c1, u32 c0) {
         const u32 L1 = (u32)-(int)((l1w >> j) & 1ull), L0 = (u32)-(int)((l0w >> j) & 1ull);       // scalar 0 / ~0
         return bs_neq(c1, c0, L1, L0);
     }, h1, h0, f);
@@ -462,27 +463,11 @@ __device__ __forceinline__ void bs_rows_dynamic(const BsRowArgs& ra, unsigned lo
 
 // ... letters as template constants (generated code: static_generated.inc, jit.py): a column names one of the four
 // mismatch masks a row has (c1 c0 != l1 l0 for the letters 0..3); the optimiser forms each mask once per row
-template <int C, unsigned long long W1, unsigned long long W0>
+template <int C, bool SHARED, unsigned long long W1, unsigned long long W0>
 __device__ __forceinline__ void bs_rows_static(const BsRowArgs& ra, u32 (&h1)[C], u32 (&h0)[C], u32 (&f)[BS_ND]) {
-    bs_rows<C, BS_STATIC_PAIRS>(ra, [&](int j, u32 c1, u32 c0) {
+    bs_rows<C, BS_STATIC_PAIRS, SHARED>(ra, [&](int j, u32 c1, u32 c0) {
         return bs_neq_letter((int)((W1 >> j) & 1ull) * 2 + (int)((W0 >> j) & 1ull), c1, c0);
     }, h1, h0, f);
-}
-
-// 32 x 32 bit matrix in registers, transposed in place: out[b] bit k = in[k] bit b (five butterfly stages of 16 word pairs)
-__device__ __forceinline__ void bs_transpose32(u32 (&a)[32]) {
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-        const int j = 16 >> s;
-        const u32 m = s == 0 ? 0x0000FFFFu : (s == 1 ? 0x00FF00FFu : (s == 2 ? 0x0F0F0F0Fu : (s == 3 ? 0x33333333u : 0x55555555u)));
-#pragma unroll
-        for (int k = 0; k < 32; ++k) {
-            if (k & j) continue;
-            const u32 lo = a[k], hi = a[k + j];
-            a[k] = (lo & m) | ((hi & m) << j);
-            a[k + j] = ((lo >> j) & m) | (hi & ~m);
-        }
-    }
 }
 
 struct BsArgs {                                // one struct: run-time generated kernels are launched with a single parameter
@@ -584,7 +569,7 @@ template <class G>
 __device__ __forceinline__ void bs_barcode_body(const BsArgs& args) {
     constexpr int C = G::C;
     __shared__ uint4 s_rows[BS_MAX_ROWS * 64];                  // per row and lane: c1, c0, dv + 1 at the last shared column
-    __shared__ u32 s_tail[3 * BS_NB * 64];                      // last row after the shared columns: sum, maximum; maximum of the trailing columns' last row
+    __shared__ u32 s_tail[3 * BS_NB * 64];                      // last row after the shared columns: H(L,P) + 64 - C, the row maximum's deficit (BS_NE planes); maximum of the trailing columns' last row
     __shared__ u32 s_unit;
     __shared__ u32 s_draw;                                      // next barcode of the unit (BsArgs::draw)
     __shared__ u32 s_ready;                                     // a SOLO unit's shared-column progress (bs_shared_columns)
@@ -764,13 +749,13 @@ __device__ __forceinline__ void bs_barcode_body(const BsArgs& args) {
             if (wave == BS_WAVES - 1) {
                 __builtin_amdgcn_s_setprio(3);                            // (the barcode waves rotate through 0..3: the producer must not starve)
                 if constexpr (G::KERNEL >= 0 && QCAT_BS_STATIC_SHARED) {
-                    if constexpr (G::PRE > 0) bs_shared_columns_static<G::PRE, G::S1, G::S0, true>(s_rows, s_tail, L, lane, wave, &s_ready, s_hold, npad);
+                    if constexpr (G::PRE > 0) bs_shared_columns_static<G::PRE, G::S1, G::S0, true>(s_rows, s_tail, L, lane, wave, &s_ready, s_hold, npad, C);
                 } else {
                     const u32 l1 = (u32)uni(bits[4 * b0]), l0 = (u32)uni(bits[4 * b0 + 2]);
                     switch (P) {
-                    case 4: bs_shared_columns_dynamic<4, true>(s_rows, s_tail, L, lane, wave, l1, l0, &s_ready, s_hold, npad); break;
-                    case 8: bs_shared_columns_dynamic<8, true>(s_rows, s_tail, L, lane, wave, l1, l0, &s_ready, s_hold, npad); break;
-                    default: bs_shared_columns_dynamic<11, true>(s_rows, s_tail, L, lane, wave, l1, l0, &s_ready, s_hold, npad); break;
+                    case 4: bs_shared_columns_dynamic<4, true>(s_rows, s_tail, L, lane, wave, l1, l0, &s_ready, s_hold, npad, C); break;
+                    case 8: bs_shared_columns_dynamic<8, true>(s_rows, s_tail, L, lane, wave, l1, l0, &s_ready, s_hold, npad, C); break;
+                    default: bs_shared_columns_dynamic<11, true>(s_rows, s_tail, L, lane, wave, l1, l0, &s_ready, s_hold, npad, C); break;
                     }
                 }
                 __builtin_amdgcn_s_setprio(0);
@@ -787,19 +772,19 @@ __device__ __forceinline__ void bs_barcode_body(const BsArgs& args) {
             if (wave < BS_PRE_WAVES) {
                 bool done = false;
                 if constexpr (G::KERNEL >= 0 && QCAT_BS_STATIC_SHARED) {     // the family's leading context is a compile-time constant
-                    if constexpr (G::PRE > 0) { bs_shared_columns_static<G::PRE, G::S1, G::S0, false>(s_rows, s_tail, L, lane, wave, nullptr, s_hold, npad); done = true; }
+                    if constexpr (G::PRE > 0) { bs_shared_columns_static<G::PRE, G::S1, G::S0, false>(s_rows, s_tail, L, lane, wave, nullptr, s_hold, npad, C); done = true; }
                 } else {
                     const u32 l1 = (u32)uni(bits[4 * b0]), l0 = (u32)uni(bits[4 * b0 + 2]);     // the shared columns: any barcode's
                     switch (P) {
-                    case 4: bs_shared_columns_dynamic<4, false>(s_rows, s_tail, L, lane, wave, l1, l0, nullptr, s_hold, npad); done = true; break;
-                    case 8: bs_shared_columns_dynamic<8, false>(s_rows, s_tail, L, lane, wave, l1, l0, nullptr, s_hold, npad); done = true; break;
-                    case 11: bs_shared_columns_dynamic<11, false>(s_rows, s_tail, L, lane, wave, l1, l0, nullptr, s_hold, npad); done = true; break;
+                    case 4: bs_shared_columns_dynamic<4, false>(s_rows, s_tail, L, lane, wave, l1, l0, nullptr, s_hold, npad, C); done = true; break;
+                    case 8: bs_shared_columns_dynamic<8, false>(s_rows, s_tail, L, lane, wave, l1, l0, nullptr, s_hold, npad, C); done = true; break;
+                    case 11: bs_shared_columns_dynamic<11, false>(s_rows, s_tail, L, lane, wave, l1, l0, nullptr, s_hold, npad, C); done = true; break;
                     default: break;
                     }
                 }
-                if (!done && wave == 0) {
+                if (!done && wave == 0) {                                  // no shared columns: bs_last_row_start with P = 0
 #pragma unroll
-                    for (int q = 0; q < BS_NB; ++q) { s_tail[q * 64 + lane] = (BS_OFF >> q) & 1 ? 0xFFFFFFFFu : 0u; s_tail[(BS_NB + q) * 64 + lane] = 0u; }
+                    for (int q = 0; q < BS_NB; ++q) { s_tail[q * 64 + lane] = ((BS_OFF - C) >> q) & 1 ? 0xFFFFFFFFu : 0u; s_tail[(BS_NB + q) * 64 + lane] = 0u; }
                 }
             } else if (wave < 2 * BS_PRE_WAVES) {
                 bs_trailing_of<G, false>(s_rows, rp, s_tail, L, lane, wave - BS_PRE_WAVES, Q, tl1, tl0, nullptr, s_hold, npad);    // (wave w and wave w + 4 share a SIMD: one context each)
@@ -809,7 +794,7 @@ __device__ __forceinline__ void bs_barcode_body(const BsArgs& args) {
             BS_STAMP(5);
         }
         const int nb_waves = min(BS_WAVES, b1 - b0);                       // waves that walk barcodes: wave w sits on SIMD w % 4
-        const BsRowArgs ra{s_rows, L, lane, P != 0, solo ? &s_ready : nullptr, max(1, (nb_waves - (wave & 3) + 3) / 4), rp, solo ? &s_ready_r : nullptr, npad, s_hold};
+        const BsRowArgs ra{s_rows, L, lane, solo ? &s_ready : nullptr, max(1, (nb_waves - (wave & 3) + 3) / 4), rp, solo ? &s_ready_r : nullptr, npad, s_hold};
 
         u32 bestv[BS_NB], besti[BS_NB];
 #pragma unroll
@@ -836,17 +821,21 @@ __device__ __forceinline__ void bs_barcode_body(const BsArgs& args) {
             } else {
                 const unsigned long long l1w = ((unsigned long long)(u32)uni(bits[4 * b]) | ((unsigned long long)(u32)uni(bits[4 * b + 1]) << 32)) >> P;
                 const unsigned long long l0w = ((unsigned long long)(u32)uni(bits[4 * b + 2]) | ((unsigned long long)(u32)uni(bits[4 * b + 3]) << 32)) >> P;
-                bs_rows_dynamic<C>(ra, l1w, l0w, h1, h0, f);
+                if (P != 0) bs_rows_dynamic<C, true>(ra, l1w, l0w, h1, h0, f);
+                else bs_rows_dynamic<C, false>(ra, l1w, l0w, h1, h0, f);
             }
-            // last row: H(L, j) = sum of dh(L, 1..j), continued after the shared columns up to the line in front of the trailing
-            // context; then raw = max(H(L, c) + deficit, the last row's maximum, the trailing columns' own maximum) (bs_core.h)
-            u32 r[BS_NB], rowbest[BS_NB], cmax[BS_NB];
+            // last row: raw = max(H(L, c) + deficit, the last row's maximum, the trailing columns' own maximum) (bs_core.h)
+            // (round 7: the row maximum as a deficit and H(L, c) as one carry-save sum of the codes instead of a counter step and a
+            // maximum per column -- bs_core.h: bs_last_row)
+            u32 rowbest[BS_NB];
             bs_wait_rows(ra.ready, L + 1);                               // (SOLO: the producer's tail)
-#pragma unroll
-            for (int q = 0; q < BS_NB; ++q) { r[q] = s_tail[q * 64 + lane]; rowbest[q] = s_tail[(BS_NB + q) * 64 + lane]; cmax[q] = s_tail[(2 * BS_NB + q) * 64 + lane]; }
-#pragma unroll
-            for (int j = 0; j < C; ++j) { bs_step(r, h1[j], h0[j]); bs_max(rowbest, r); }
-            bs_finish_split(rowbest, r, f, cmax);
+            const auto tail = [&](int q) { return s_tail[q * 64 + lane]; };
+            if constexpr (G::KERNEL >= 0) {
+                bs_last_row<C, G::PRE != 0>(rowbest, h1, h0, tail, f);
+            } else {
+                if (P != 0) bs_last_row<C, true>(rowbest, h1, h0, tail, f);
+                else bs_last_row<C, false>(rowbest, h1, h0, tail, f);
+            }
             // keep (raw, smallest index): a wave's barcodes come in increasing index order, so strictly greater replaces
             const u32 gt = bs_gt(rowbest, bestv);
 #pragma unroll
@@ -873,19 +862,27 @@ __device__ __forceinline__ void bs_barcode_body(const BsArgs& args) {
         for (int q = tid; q < BS_JOBS; q += BS_WAVES * 64) s_keys[q] = 0u;
         __syncthreads();
         if (had) {
-#pragma unroll 4
-            for (int bit = 0; bit < 32; ++bit) {
-                u32 val = 0, idx = 0;
+            // (round 7: the keys are a bit-matrix transposition of the planes -- bs_core.h: bs_keys32 -- not 14 bits picked per alignment)
+            static_assert(BS_OFF == 64 && BS_NB == 7, "bs_keys32 spells barcode_key(raw, b) out in planes");
+            u32 key[32];
+            bs_keys32(key, bestv, besti);
 #pragma unroll
-                for (int q = 0; q < BS_NB; ++q) { val |= ((bestv[q] >> bit) & 1u) << q; idx |= ((besti[q] >> bit) & 1u) << q; }
-                atomicMax(&s_keys[bit * 64 + lane], barcode_key((int)val - BS_OFF, (int)idx));
-            }
+            for (int bit = 0; bit < 32; ++bit) atomicMax(&s_keys[bit * 64 + lane], key[bit]);
         }
         __syncthreads();
         {
             u32* __restrict__ dst = keys + (size_t)chunk * key_stride + pos0;
             const int covered = (int)min((uint32_t)BS_JOBS, uni((int)(bp->first[bin] + bp->cov[bin] - pos0)));    // (a padded super-tile: its jobs only)
-            for (int q = tid; q < covered; q += BS_WAVES * 64) dst[q] = s_keys[(q & 31) * 64 + (q >> 5)];
+            static_assert(BS_JOBS % (BS_WAVES * 64) == 0, "whole passes of the workgroup");
+            // (a fixed trip count and an index the optimiser cannot see through: neither the loop's set-up nor the addresses it forms
+            // from the thread index are hoisted out of the unit loop, where they would hold registers through every barcode's rows)
+            int t = tid;
+            asm volatile("" : "+v"(t));
+#pragma unroll
+            for (int pass = 0; pass < BS_JOBS / (BS_WAVES * 64); ++pass) {
+                const int q = t + pass * (BS_WAVES * 64);
+                if (q < covered) dst[q] = s_keys[(q & 31) * 64 + (q >> 5)];
+            }
         }
     }
 }

@@ -294,7 +294,7 @@ def generate(descriptor, skip_templates=(), skip_groups=()):
                              "u32 (&h1)[C], u32 (&h0)[C], u32 (&f)[BS_ND]) {\n        switch (kase) {\n" % (g, own, g, pre, post, s1, s0, t1, t0))
                 for b, tg in enumerate(targets):
                     w1, w0 = _bs_words(tg, rev, pre, own)
-                    parts.append("        case %d: bs_rows_static<C, 0x%XULL, 0x%XULL>(ra, h1, h0, f); break;\n" % (b, w1, w0))
+                    parts.append("        case %d: bs_rows_static<C, PRE != 0, 0x%XULL, 0x%XULL>(ra, h1, h0, f); break;\n" % (b, w1, w0))
                 parts.append("        default: break;\n        }\n    }\n};\n")
                 entry.append('extern "C" __global__ void __launch_bounds__(qk::BS_WAVES * 64) '
                              "qj_bs_%d(qk::BsArgs a) { qk::bs_barcode_body<qk::QBSJ_%d>(a); }\n" % (g, g))

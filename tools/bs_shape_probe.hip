@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(1024) k_rows(ProbeArgs a) {
     unsigned long long t0 = 0, t1 = 0, r0 = 0, r1 = 0;
     u32 acc = 0;
     if (wave < a.active) {
-        const BsRowArgs ra{s_rows, a.L, lane, true, nullptr, 4, rp, nullptr, 0, nullptr};
+        const BsRowArgs ra{s_rows, a.L, lane, nullptr, 4, rp, nullptr, 0, nullptr};
         t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime();
         for (int rep = 0; rep < a.reps; ++rep)
             for (int b = 0; b < a.nb; ++b) {

@@ -268,7 +268,7 @@ def render():
                         if half == 1 and tb == ta:
                             continue
                         w1, w0 = bs_words(t, rev, pre, CODE, own)
-                        bh.write("        case %d: bs_rows_static<C, 0x%XULL, 0x%XULL>(ra, h1, h0, f); break;\n"
+                        bh.write("        case %d: bs_rows_static<C, PRE != 0, 0x%XULL, 0x%XULL>(ra, h1, h0, f); break;\n"
                                  % (2 * pr + half, w1, w0))
                 bh.write("        default: break;\n        }\n    }\n};\n")
                 bs_structs.append((kid, len(targets), "".join(bh.parts)))
