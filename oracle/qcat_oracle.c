@@ -683,8 +683,16 @@ int qo_scan_batch(const qcat_kit_desc* d, const uint8_t* bases, const uint64_t* 
 
 /* BarcodeScanner.scan() of whole sequences of any length (scanner_epi2me.py:33-144 / scanner_dual.py:35-146):
  * the checker of qcat_scan_sequences.  One record per sequence, exactly what scan() returns. */
+int qo_scan_sequences_trace(const qcat_kit_desc* d, const uint8_t* bases, const uint64_t* offsets,
+                            uint32_t n_seqs, qcat_result* out, qcat_end_trace* traces);
 int qo_scan_sequences(const qcat_kit_desc* d, const uint8_t* bases, const uint64_t* offsets,
                       uint32_t n_seqs, qcat_result* out) {
+    return qo_scan_sequences_trace(d, bases, offsets, n_seqs, out, NULL);
+}
+
+/* ... with one trace per sequence (or NULL): the template taken, the region / whole-window path and the barcode regions */
+int qo_scan_sequences_trace(const qcat_kit_desc* d, const uint8_t* bases, const uint64_t* offsets,
+                            uint32_t n_seqs, qcat_result* out, qcat_end_trace* traces) {
     qo_kit* k = NULL;
     int rc = qo_kit_prepare(d, &k);
     if (rc) return rc;
@@ -693,7 +701,9 @@ int qo_scan_sequences(const qcat_kit_desc* d, const uint8_t* bases, const uint64
         int64_t len = (int64_t)(offsets[r + 1] - offsets[r]);
         uint8_t* w = (uint8_t*)malloc((size_t)len + 1);
         for (int64_t i = 0; i < len; ++i) w[i] = qo_code_of[seq[i]];
-        qo_scan s = d->mode == QCAT_MODE_SIMPLE ? qo_scan_simple(k, w, (int)len, NULL, NULL) : qo_scan_end(k, w, (int)len, NULL, NULL, 0);
+        qcat_end_trace* tr = traces ? traces + r : NULL;
+        if (tr) memset(tr, 0, sizeof *tr);
+        qo_scan s = d->mode == QCAT_MODE_SIMPLE ? qo_scan_simple(k, w, (int)len, tr, NULL) : qo_scan_end(k, w, (int)len, tr, NULL, 0);
         qo_to_record(&s, 0, 0, &out[r]);
         free(w);
     }

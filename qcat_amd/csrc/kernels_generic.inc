@@ -287,7 +287,7 @@ __device__ inline bool dev_middle_strand(const KitPtrs& kp, const uint8_t* read,
     const DevTpl& p = k->tpl[r.used_tpl];
     const int nsets = k->mode == QCAT_MODE_DUAL ? 2 : 1;
     for (int s = 0; s < nsets; ++s)
-        if (r.bc_idx[s] < 0 || r.bc_raw[s] < p.sets[s].min_raw_middle) return false;   // barcode None / score < 50 (dual: min of both)
+        if ((r.bc_idx[s] < 0 ? 0 : r.bc_raw[s]) < p.sets[s].min_raw_middle) return false;   // barcode None (scores 0.0) / score < 50 (dual: min of both)
     return true;
 }
 

@@ -454,8 +454,18 @@ k_mid_finalize(const DevKit* __restrict__ k, const EndRec* __restrict__ mrecs, c
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_reads) return;
     const uint32_t slot = mslot[r];
-    if (slot == 0xFFFFFFFFu) return;
     const int nsets = k->mode == QCAT_MODE_DUAL ? 2 : 1;
+    if (slot == 0xFFFFFFFFu) {
+        // no slot and not left to the general kernel: no called adapter, or no interior (read[n:-n] is empty).  The scan of an
+        // empty interior finds no barcode, which the reference scores 0.0: a hit only under a threshold of 0 or less
+        if (!k->middle_hits_empty || generic_flag[r]) return;
+        qcat_result res = results[r];
+        if (res.adapter_idx < 0) return;
+        res.barcode_idx = -1; res.barcode2_idx = -1; res.adapter_idx = -1; res.exit_status = 997;
+        res.adapter_end = 0; res.raw_score = 0; res.score_den = 1;
+        results[r] = res;
+        return;
+    }
     // a barcode region longer than an end window (Python's slice wrap when the adapter ends within the interior's first
     // few bases, qcat/scanner_base.py:29-60, gives interior[0 : L - x]) is beyond the rows the barcode kernels hold:
     // the general kernel, which runs after this one over the flagged reads, decides for that read
@@ -467,7 +477,8 @@ k_mid_finalize(const DevKit* __restrict__ k, const EndRec* __restrict__ mrecs, c
         const EndRec rec = mrecs[slot + st];
         const DevTpl& p = k->tpl[rec.used_tpl];
         bool ok = true;
-        for (int s = 0; s < nsets; ++s) ok = ok && rec.bc_idx[s] >= 0 && rec.bc_raw[s] >= p.sets[s].min_raw_middle;
+        // (barcode None scores 0.0 in the reference: below every positive threshold, not below one of 0 or less)
+        for (int s = 0; s < nsets; ++s) ok = ok && (rec.bc_idx[s] >= 0 ? rec.bc_raw[s] : 0) >= p.sets[s].min_raw_middle;
         hit = ok;
     }
     if (hit) {

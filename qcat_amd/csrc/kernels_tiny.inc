@@ -391,7 +391,7 @@ k_midw_finish(MidWaveArgs a) {
                 const int16_t* sc = a.sc + ((size_t)id * 2 + s) * a.sc_stride;
                 for (int b = 0; b < bs.n; ++b) { const int v = sc[b]; if (bi < 0 || braw == 0 || braw < v) { bi = b; braw = v; } }
             }
-            if (bi < 0 || braw < bs.min_raw_middle) ok = false;      // barcode None / score < 50 (dual: min of both)
+            if ((bi < 0 ? 0 : braw) < bs.min_raw_middle) ok = false;      // barcode None (scores 0.0) / score < 50 (dual: min of both)
         }
         hit = ok;
     }

@@ -126,7 +126,9 @@ struct DevKit {
     int32_t abs_ok;             // the adapter scoring is +5 / -2 / N -1 / gap 2 and every template is made of A, T, G, C, N:
                                 // the bit-sliced adapter kernels (kernels_abs.inc) are exact for this kit
     int8_t amat[49], bmat[49];
-    int8_t pad_[2];             // (sizeof stays a multiple of 4)
+    int8_t middle_hits_empty;   // --detect-middle: an interior scan that finds no barcode (or an empty interior) scores 0.0 in the
+                                // reference, a hit when middle_min_score <= 0 (never at the product's 50.0)
+    int8_t pad_[1];             // (sizeof stays a multiple of 4)
     DevTpl tpl[MAX_T];
 };
 

@@ -99,6 +99,7 @@ int kit_prepare(const qcat_kit_desc* d, HostKit* hk, std::string* err) {
     k.max_align = d->max_align_length; k.ext = d->extracted_barcode_extension;
     k.n_barcode_slots = d->n_barcode_slots; k.n_kit_slots = d->n_kit_slots;
     k.scan_middle = (d->scan_middle_adapter && d->ends == QCAT_ENDS_BOTH) ? 1 : 0;
+    k.middle_hits_empty = smallest_raw(1.0, d->middle_min_score, false) <= 0 ? 1 : 0;     // (0 * 100.0 / tlen >= middle_min_score)
     k.n_buckets = ((d->mode == QCAT_MODE_DUAL) ? d->n_barcode_slots * d->n_barcode_slots : d->n_barcode_slots)
                   + 1 + d->n_kit_slots + 1 + 1;              // [barcodes.., none][kits.., none][skipped]
     k.min_read_length = d->min_read_length > 0 ? d->min_read_length : 0;
