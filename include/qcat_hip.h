@@ -61,7 +61,9 @@ typedef enum qcat_mode {
      * window (find_highest_scoring_barcode without contexts, scanner_base.py:63-141), the winner is reported when
      * its score reaches min_quality, `adapter` is None and adapter_end is the winner's end_query.  The descriptor
      * carries one template of length 0 whose sets[0] is the barcode list (bc_len[0] = barcode length,
-     * bc_start / bc_end = -1); general int32 kernel. */
+     * bc_start / bc_end = -1).  A list of ONE length between 16 and 64 letters, windows of at most 150 bases and a
+     * barcode matrix that binary16 lanes hold run the packed end-tracking kernels (qcat_kit_info.packed = 1;
+     * QCAT_HIP_NO_SIMPLE_PACKED=1 forces the other path); everything else the general int32 kernel. */
     QCAT_MODE_SIMPLE = 2
 } qcat_mode;
 
@@ -212,7 +214,8 @@ int  qcat_kit_count_buckets(const qcat_kit* kit);
 /* Which kernels a prepared kit will run (no reference counterpart: the reference has one code
  * path; this reports the library's choice so callers and tests can see a fall-back).
  *   packed            1: packed inter-read DP kernels, 0: generic per-read kernel (affine gaps,
- *                     scores outside the packed range, templates / targets too long)
+ *                     scores outside the packed range, templates / targets too long; QCAT_MODE_SIMPLE:
+ *                     a list of unequal lengths or of a length outside 16..64)
  *   barcode_f16       1: barcode DP in exact-integer binary16 lanes, 0: u16 lanes
  *   adapter_f16       1: the binary16 adapter DP is exact for this kit
  *   n_templates / n_static_templates   adapter templates / those bound to a generated
@@ -517,7 +520,9 @@ typedef struct qcat_demux_stats {
 } qcat_demux_stats;
 /* scans every read of the file with `kit` (QCAT_ENDS_BOTH) and writes the outputs; recs[r] / skipped[r] (n_reads entries
  * each, caller-owned) receive the record of read r and whether the minimum-length filter dropped it.
- * QCAT_ERR_UNSUPPORTED: simple mode, or kit_auto with a kit whose adapter pass cannot be resumed per kit. */
+ * QCAT_MODE_SIMPLE: a record is a call when barcode_idx >= 0 with adapter_idx == -1; names and ids come from template 0
+ * (the list), the TSV kit column reads "None"; kit_auto must be 0 (QCAT_ERR_ARG).
+ * QCAT_ERR_UNSUPPORTED: kit_auto with a kit whose adapter pass cannot be resumed per kit. */
 int  qcat_fastq_demux(qcat_fastq* f, qcat_ctx* ctx, const qcat_kit* kit, const qcat_demux_opts* opts,
                       qcat_result* recs, uint8_t* skipped, qcat_demux_stats* stats);
 
@@ -545,7 +550,9 @@ int  qcat_fastq_demux(qcat_fastq* f, qcat_ctx* ctx, const qcat_kit* kit, const q
  * with stats->incomplete = 1, stats->next_offset = the file offset of the segment's first record and stats->n_reads = the
  * reads handled so far, and the caller's own parser carries on from there.  On ANY failure stats->n_reads / ->segments say
  * how much had been written when it happened (QCAT_ERR_UNSUPPORTED with both 0: nothing was -- the caller may redo the
- * file itself; anything else is an error behind written output). */
+ * file itself; anything else is an error behind written output).
+ * QCAT_MODE_SIMPLE is taken like the other modes (kit_auto 0): every kept read counts under n_adapter_none, a call
+ * (barcode_idx >= 0, adapter_idx == -1) under barcode[(0 * w0 + b) * w1]. */
 typedef struct qcat_demux_hist {
     int32_t w0, w1;            /* in: row widths -- w0 >= the largest set 0, w1 >= the largest set 1 (dual mode), else 1 */
     int64_t* barcode;          /* out [n_templates * w0 * w1]: kept reads per (template t, barcode b, second barcode b2) at (t * w0 + b) * w1 + b2 */

@@ -324,11 +324,14 @@ def _native_demux(detector, reads_fq, nobatch, out, tsv, stream, trim, min_read_
     written).  A resume offset means the native loop ended in front of a record that is not a plain one (a wrapped or blank
     line ...): the reads before it are done and written, the caller's own parser takes the rest of the file."""
     from . import native
-    layouts = detector.layouts
+    simple = detector._native_mode == "simple"
+    # simple mode: the one barcode list as the only "template" -- names and ids come from it, no kit to vote for, and every
+    # kept read counts under adapter "none" (the native loop's n_adapter_none)
+    layouts = [detector._simple_layout] if simple else detector.layouts
     if not layouts:
         return None
     one_kit = len(set(l.kit for l in layouts)) == 1
-    kit_auto = (not nobatch) and not one_kit            # per-batch vote (detect_barcode_batch); one kit: nothing to vote on
+    kit_auto = (not nobatch) and not one_kit and not simple   # per-batch vote (detect_barcode_batch); one kit: nothing to vote on
     kit = detector._native_kit(layouts, qcat_config, native.ENDS_BOTH)
     if out and not os.path.exists(out):
         os.makedirs(out)
@@ -400,10 +403,10 @@ def qcat_cli(reads_fq, kit, mode, nobatch, out, min_qual, tsv, output, threads, 
     fastq = is_fastq(reads_fq)
     stream = open(output, "w") if output else sys.stdout
     native_done = None
-    if mode in ("epi2me", "dual") and not os.environ.get("QCAT_AMD_NO_NATIVE_FASTQ"):
+    if (mode in ("epi2me", "dual") or (mode == "simple" and not middle_adapter)) and not os.environ.get("QCAT_AMD_NO_NATIVE_FASTQ"):
         # plain four-line FASTQ files and plain two-line FASTA files go through the native ingest / egress
         # (qcat_fastq_demux_stream): same outputs, no Python string per read, --detect-middle and --filter-barcodes included;
-        # anything else (stdin, wrapped or odd records, simple mode) stays on -- or comes back to -- the loop below
+        # anything else (wrapped or odd records, --simple with --detect-middle) stays on -- or comes back to -- the loop below
         native_done = _native_demux(detector, reads_fq, nobatch, out, tsv, stream, trim, min_read_length, qcat_config, tsv_stream,
                                     filter_barcodes=filter_barcodes)
     barcode_dist, adapter_dist, total_reads, skipped_reads, resume = {}, {}, 0, 0, 0

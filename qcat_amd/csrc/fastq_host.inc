@@ -360,7 +360,8 @@ namespace qk {
 struct FqWriter {
     const DevKit& hk;
     const qcat_demux_opts* o;
-    bool dual, fasta, to_dir, write_reads;
+    bool dual, simple, fasta, to_dir, write_reads;
+    const std::string none_kit = "None";
     std::vector<std::string> kit_name;
     std::vector<std::vector<std::string>> bname, bid, bid2;
     std::vector<std::vector<int>> bnum, bnum2;
@@ -389,7 +390,7 @@ struct FqWriter {
     double t_write = 0, t_format = 0;                            // busy time of the writers; of which formatting (the rest: write calls)
     size_t max_id_len = 4, max_kit_len = 4;                      // longest barcode id / kit name of the tables ("none" / "None" at least)
 
-    FqWriter(const DevKit& k, const qcat_demux_opts* opts, bool fasta_) : hk(k), o(opts), dual(k.mode == QCAT_MODE_DUAL), fasta(fasta_) {
+    FqWriter(const DevKit& k, const qcat_demux_opts* opts, bool fasta_) : hk(k), o(opts), dual(k.mode == QCAT_MODE_DUAL), simple(k.mode == QCAT_MODE_SIMPLE), fasta(fasta_) {
         to_dir = o->out_dir != nullptr && o->out_dir[0];
         write_reads = to_dir || !o->tsv;                         // qcat/cli.py:553: `if out or not tsv`
         nthreads = std::max(1u, host_threads());
@@ -455,9 +456,12 @@ struct FqWriter {
     }
     // a call needs every index inside the caller's tables (k_finalize never writes a first barcode without the second in dual
     // mode; an index outside a table is treated as "not called" rather than read past the table)
+    // (simple mode: no adapter -- a record is called when it names a barcode with adapter_idx == -1; names and ids come from
+    // template 0, the one list, and the TSV kit column reads "None" as cli.tsv_row prints `result["adapter"] is None`)
+    inline size_t tpl_of(const qcat_result& q) const { return simple ? 0 : (size_t)q.adapter_idx; }
     inline bool called(const qcat_result& q) const {
-        if (!(q.barcode_idx >= 0 && q.adapter_idx >= 0 && q.adapter_idx < hk.nt)) return false;
-        const size_t t = (size_t)q.adapter_idx;
+        if (simple ? !(q.barcode_idx >= 0 && q.adapter_idx == -1) : !(q.barcode_idx >= 0 && q.adapter_idx >= 0 && q.adapter_idx < hk.nt)) return false;
+        const size_t t = tpl_of(q);
         return (size_t)q.barcode_idx < bnum[t].size() && (!dual || (q.barcode2_idx >= 0 && (size_t)q.barcode2_idx < bnum2[t].size()));
     }
     // formats and writes `cnt` consecutive reads (records x[], results res[], flags skipped[], bytes at `data`): `nthreads`
@@ -515,7 +519,7 @@ struct FqWriter {
                 const bool called = this->called(q);
                 const std::string* name_s = nullptr; const std::string* id_s = nullptr;
                 if (called) {
-                    const size_t t = (size_t)q.adapter_idx;
+                    const size_t t = tpl_of(q);
                     if (dual) {
                         const int a = bnum[t][(size_t)q.barcode_idx], b2 = bnum2[t][(size_t)q.barcode2_idx];
                         snprintf(num, sizeof num, "barcode%02d/%02d", a, b2);
@@ -546,7 +550,7 @@ struct FqWriter {
                             st.len = (uint8_t)fq_repr_double(score, st.text); st.key = key;
                         }
                         memcpy(w, st.text, st.len); w += st.len; *w++ = '\t';
-                        const std::string& kn = kit_name[(size_t)q.adapter_idx];
+                        const std::string& kn = simple ? none_kit : kit_name[(size_t)q.adapter_idx];
                         memcpy(w, kn.data(), kn.size()); w += kn.size(); *w++ = '\t';
                         w = std::to_chars(w, w + 20, (int64_t)q.adapter_end).ptr; *w++ = '\t';
                     } else {
@@ -564,7 +568,7 @@ struct FqWriter {
                 if (write_reads) {
                     std::string* dst;
                     if (to_dir) {
-                        const int file = !called ? 0 : key_of[(size_t)q.adapter_idx][(size_t)q.barcode_idx * (dual ? bnum2[(size_t)q.adapter_idx].size() : 1)
+                        const int file = !called ? 0 : key_of[tpl_of(q)][(size_t)q.barcode_idx * (dual ? bnum2[(size_t)q.adapter_idx].size() : 1)
                                                                                      + (size_t)(dual ? q.barcode2_idx : 0)];
                         dst = &bo.fbuf[(size_t)file];
                         if (dst->empty()) bo.used.push_back(file);
@@ -698,7 +702,7 @@ static inline void fq_filter_batch(const FqWriter& w, qcat_result* res, uint64_t
     std::map<uint64_t, uint64_t> count;                          // key: id (dual: both ids); ~0: none
     auto key_of = [&](const qcat_result& q) -> uint64_t {
         if (!w.called(q)) return ~0ull;
-        const size_t t = (size_t)q.adapter_idx;
+        const size_t t = w.tpl_of(q);
         const uint64_t a = (uint32_t)w.bnum[t][(size_t)q.barcode_idx];
         return w.dual ? (a << 32) | (uint32_t)w.bnum2[t][(size_t)q.barcode2_idx] : a;
     };
@@ -723,7 +727,7 @@ extern "C" int qcat_fastq_demux(qcat_fastq* f, qcat_ctx* c, const qcat_kit* ckit
     if (!f || !c || !ckit || !o || !recs || !skipped) return set_err(QCAT_ERR_ARG, "qcat_fastq_demux: null argument");
     qcat_kit* kit = const_cast<qcat_kit*>(ckit);
     const DevKit& hk = kit->hk.dk;
-    if (hk.mode == QCAT_MODE_SIMPLE) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_fastq_demux: simple mode is not covered");
+    if (hk.mode == QCAT_MODE_SIMPLE && o->kit_auto) return set_err(QCAT_ERR_ARG, "qcat_fastq_demux: simple mode has no kits to vote for (kit_auto must be 0)");
     if (hk.ends != QCAT_ENDS_BOTH) return set_err(QCAT_ERR_ARG, "qcat_fastq_demux needs a kit created with QCAT_ENDS_BOTH");
     const uint64_t n = f->recs.size();
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };

@@ -474,7 +474,7 @@ extern "C" int qcat_fastq_demux_stream(const char* path, qcat_ctx* c, const qcat
     if ((!path && !(o && o->input_fd > 0)) || !c || !ckit || !o || !hist || !stats) return set_err(QCAT_ERR_ARG, "qcat_fastq_demux_stream: null argument");
     qcat_kit* kit = const_cast<qcat_kit*>(ckit);
     const DevKit& hk = kit->hk.dk;
-    if (hk.mode == QCAT_MODE_SIMPLE) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_fastq_demux_stream: simple mode is not covered");
+    if (hk.mode == QCAT_MODE_SIMPLE && o->kit_auto) return set_err(QCAT_ERR_ARG, "qcat_fastq_demux_stream: simple mode has no kits to vote for (kit_auto must be 0)");
     if (hk.ends != QCAT_ENDS_BOTH) return set_err(QCAT_ERR_ARG, "qcat_fastq_demux_stream needs a kit created with QCAT_ENDS_BOTH");
     const bool dual = hk.mode == QCAT_MODE_DUAL;
     if (hist->w0 < 1 || hist->w1 < 1 || !hist->barcode || !hist->adapter) return set_err(QCAT_ERR_ARG, "qcat_fastq_demux_stream: histogram arrays missing");
@@ -611,7 +611,7 @@ extern "C" int qcat_fastq_demux_stream(const char* path, qcat_ctx* c, const qcat
                     if (s.skipped[r]) { ++n_skipped; continue; }
                     const qcat_result& q = s.res[r];
                     if (q.adapter_idx >= 0 && q.adapter_idx < hk.nt) ++hist->adapter[q.adapter_idx]; else ++hist->n_adapter_none;
-                    if (w.called(q)) ++hist->barcode[((size_t)q.adapter_idx * (size_t)hist->w0 + (size_t)q.barcode_idx) * (size_t)hist->w1 + (size_t)(dual ? q.barcode2_idx : 0)];
+                    if (w.called(q)) ++hist->barcode[(w.tpl_of(q) * (size_t)hist->w0 + (size_t)q.barcode_idx) * (size_t)hist->w1 + (size_t)(dual ? q.barcode2_idx : 0)];
                     else ++hist->n_none;
                 }
                 n_written += s.n_use;

@@ -371,8 +371,34 @@ k_scan_sequences(KitPtrs kp, const uint8_t* __restrict__ bases, const uint64_t* 
 // k_scan_simple: BarcodeScannerSimple.scan (qcat/scanner_simple.py:41-91) of one read-end window per
 // thread: find_highest_scoring_barcode over the kit's ONE barcode list, no contexts, the WHOLE window as
 // the query (scanner_base.py:63-141, rule R2 incl.); the winner's end_query becomes adapter_end.
-// General int32 DP (the barcode kernels of the other modes do not track end positions).
+// General int32 DP: ragged lists, lengths without a width class and matrices outside binary16 (every other simple kit runs
+// kernels_simple.inc), and the cross-check of those kernels (QCAT_HIP_NO_SIMPLE_PACKED=1).
 // ---------------------------------------------------------------------------------------------
+// one read-end window on that routine; the packed simple kernels (kernels_simple.inc) come back here for the read ends whose
+// best raw score is exactly 0 (R2 depends on list order there)
+__device__ inline EndRec dev_simple_end(KitPtrs kp, const uint8_t* __restrict__ w, int L, uint32_t e, const int8_t* bmat, int* H, int* F,
+                                        int16_t* __restrict__ dbg_rows, uint32_t stride) {
+    const DevSet& bs = kp.kit->tpl[0].sets[0];
+    EndRec r;
+    r.window_len = L; r.best_tpl = -1; r.used_tpl = 0; r.best_end = -1; r.best_raw = -1; r.region_path = 0;
+    for (int s = 0; s < 2; ++s) { r.region_start[s] = 0; r.region_len[s] = 0; r.bc_idx[s] = -1; r.bc_raw[s] = 0; }
+    r.region_len[0] = L;
+    int bi = -1, braw = 0, bend = -1, blen = 1;
+    if (L > 0) {
+        for (int b = 0; b < bs.n; ++b) {
+            // every barcode with its own length (scanner_base.py:108-119): a user FASTA may hold barcodes of unequal length
+            const int tl = bs.len_off >= 0 ? kp.ids[bs.len_off + 3 * b] : bs.tlen;
+            const DevAlign a = dev_sg_generic(WinSeq{w}, L, kp.codes + bs.tgt_off + (size_t)b * bs.tlen, tl, 1, 1, bmat, H, F);
+            if (dbg_rows) dbg_rows[((size_t)e * 2) * stride + b] = (int16_t)a.score;
+            // `not max_score or max_score < score` on raw * 100.0 / length (:119-125): the normalised scores compared by
+            // cross-multiplication (exact: both are correctly rounded quotients of small integers)
+            if (bi < 0 || braw == 0 || braw * tl < a.score * blen) { bi = b; braw = a.score; bend = a.end_q; blen = tl; }
+        }
+    }
+    r.bc_idx[0] = bi; r.bc_raw[0] = braw; r.best_end = bend;
+    return r;
+}
+
 __global__ void __launch_bounds__(GEN_THREADS)
 k_scan_simple(KitPtrs kp, const uint8_t* __restrict__ win, const int32_t* __restrict__ wlen, uint32_t n_ends,
               EndRec* __restrict__ recs, int16_t* __restrict__ dbg_rows, uint32_t stride) {
@@ -384,28 +410,7 @@ k_scan_simple(KitPtrs kp, const uint8_t* __restrict__ win, const int32_t* __rest
     __syncthreads();
     const uint32_t e = blockIdx.x * GEN_THREADS + threadIdx.x;
     if (e >= n_ends) return;
-    const uint8_t* w = win + (size_t)e * WIN_STRIDE;
-    const int L = wlen[e];
-    const DevSet& bs = k->tpl[0].sets[0];
-    EndRec r;
-    r.window_len = L; r.best_tpl = -1; r.used_tpl = 0; r.best_end = -1; r.best_raw = -1; r.region_path = 0;
-    for (int s = 0; s < 2; ++s) { r.region_start[s] = 0; r.region_len[s] = 0; r.bc_idx[s] = -1; r.bc_raw[s] = 0; }
-    r.region_len[0] = L;
-    int bi = -1, braw = 0, bend = -1, blen = 1;
-    if (L > 0) {
-        for (int b = 0; b < bs.n; ++b) {
-            // every barcode with its own length (scanner_base.py:108-119): a user FASTA may hold barcodes of unequal length
-            const int tl = bs.len_off >= 0 ? kp.ids[bs.len_off + 3 * b] : bs.tlen;
-            const DevAlign a = dev_sg_generic(WinSeq{w}, L, kp.codes + bs.tgt_off + (size_t)b * bs.tlen, tl, 1, 1, bmat,
-                                              H + threadIdx.x, F + threadIdx.x);
-            if (dbg_rows) dbg_rows[((size_t)e * 2) * stride + b] = (int16_t)a.score;
-            // `not max_score or max_score < score` on raw * 100.0 / length (:119-125): the normalised scores compared by
-            // cross-multiplication (exact: both are correctly rounded quotients of small integers)
-            if (bi < 0 || braw == 0 || braw * tl < a.score * blen) { bi = b; braw = a.score; bend = a.end_q; blen = tl; }
-        }
-    }
-    r.bc_idx[0] = bi; r.bc_raw[0] = braw; r.best_end = bend;
-    recs[e] = r;
+    recs[e] = dev_simple_end(kp, win + (size_t)e * WIN_STRIDE, wlen[e], e, bmat, H + threadIdx.x, F + threadIdx.x, dbg_rows, stride);
 }
 
 }  // namespace qk

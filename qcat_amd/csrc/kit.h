@@ -44,12 +44,19 @@ inline int barcode_width_class(int len) {
     return 0;
 }
 
+// ... of the simple-mode kernels (kernels_simple.inc): a list of 16 to 64 letters
+inline int simple_width_class(int len) {
+    const int w[] = {24, 32, 40, 48, 56, 64};
+    for (int v : w) if (len <= v && v - len <= PADMAX) return v;
+    return 0;
+}
+
 struct DevSet {
     int32_t n, blen, tlen, uplen, downlen;
     int32_t tgt_off;            // codes blob: n * tlen target codes (up + barcode + down)
     int32_t ids_off;            // ids blob: n dense ids
     int32_t tbl_off;            // tables blob: n rows of `width` dwords, right-aligned (-1: not eligible)
-    int32_t width;              // register-array width class of the packed barcode kernel
+    int32_t width;              // register-array width class of the packed barcode kernel (an eligible simple kit: of k_simple_packed)
     int32_t min_raw_pass;       // smallest raw with raw*100.0/tlen >= min_quality
     int32_t min_raw_conflict;   // smallest raw with raw*100.0/tlen >= conflict_min_score
     int32_t min_raw_middle;     // smallest raw with raw*100.0/tlen >= middle_min_score (--detect-middle)
@@ -154,6 +161,8 @@ struct HostKit {
     int32_t ascii_tpl_off[MAX_T];
     int32_t ascii_set_off[MAX_T][2];
     int32_t bc_start[MAX_T][2];
+    int32_t simple_packed = 0;               // a simple kit the packed end-tracking kernels take (kernels_simple.inc); fast_ok stays 0:
+                                             // that flag promises adapter templates
 };
 
 int kit_prepare(const qcat_kit_desc* d, HostKit* out, std::string* err);

@@ -93,7 +93,7 @@ int kit_prepare(const qcat_kit_desc* d, HostKit* hk, std::string* err) {
 
     DevKit& k = hk->dk;
     memset(&k, 0, sizeof k);
-    hk->codes.clear(); hk->ids.clear(); hk->tables.clear(); hk->ascii.clear();
+    hk->codes.clear(); hk->ids.clear(); hk->tables.clear(); hk->ascii.clear(); hk->simple_packed = 0;
     k.mode = d->mode; k.ends = d->ends; k.nt = d->n_templates;
     k.gap_open = d->gap_open; k.gap_extend = d->gap_extend;
     k.max_align = d->max_align_length; k.ext = d->extracted_barcode_extension;
@@ -264,6 +264,20 @@ int kit_prepare(const qcat_kit_desc* d, HostKit* hk, std::string* err) {
                 }
             }
             q.width = barcode_width_class(q.tlen);
+            // simple mode on the packed end-tracking kernels (kernels_simple.inc): a list of ONE length that has a simple
+            // width class, windows of at most 150 rows, a barcode matrix the binary16 lanes hold; its tables at that width
+            if (simple && !ragged && d->max_align_length <= 150 && bf16ok && simple_width_class(q.tlen)) {
+                const int sw = simple_width_class(q.tlen);
+                const size_t off = hk->tables.size();
+                hk->tables.resize(off + (size_t)q.n * sw);
+                uint32_t sp = sp_barcode;
+                bool ok = true;
+                for (int b = 0; b < q.n && ok; ++b)
+                    ok = build_fast_tables(k.bmat, &hk->codes[q.tgt_off + (size_t)b * q.tlen], q.tlen, gb,
+                                           &hk->tables[off + (size_t)b * sw], &sp, sw, true);
+                if (ok) { sp_barcode = sp; q.tbl_off = (int32_t)off; q.width = sw; hk->simple_packed = 1; }
+                else hk->tables.resize(off);
+            }
             if (fast) {
                 size_t off = hk->tables.size();
                 hk->tables.resize(off + (size_t)q.n * q.width);

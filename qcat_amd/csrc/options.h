@@ -52,6 +52,7 @@
     X(NO_PIPELINE, "1: no chunked host pipeline") \
     X(PIPELINE_CHUNK, "reads per chunk of the host pipeline") \
     X(PIPELINE_TRACE, "1: print the split of a pipelined call") \
+    X(NO_SIMPLE_PACKED, "1: simple mode on the general kernel (k_scan_simple) instead of the packed end-tracking kernels") \
     X(NO_TINY, "1: batches of a handful of read ends take the throughput kernels like every other batch") \
     X(TINY_MAX_ENDS, "largest batch (read ends, at most 4096) on the one-wave-per-alignment kernels (default: by the number of alignments, 20000)") \
     X(AUTO_CHUNK, "batches per call of the kit-auto file loop") \

@@ -4,7 +4,8 @@
 //
 // Per batch the library enqueues on the context's stream:
 //   k_pack_windows -> [packed path: k_adapter_packed -> k_job_* -> k_barcode_packed |
-//                      generic path: k_scan_generic] -> k_finalize
+//                      generic path: k_scan_generic |
+//                      simple mode: k_simple_packed -> k_simple_select (or k_scan_simple)] -> k_finalize
 // (see DESIGN.md for the data layout and the roofline of each kernel).
 #include <hip/hip_runtime.h>
 
@@ -32,6 +33,7 @@
 #include "kernels_tiny.inc"
 #include "kernels_packed.inc"
 #include "kernels_bitslice.inc"
+#include "kernels_simple.inc"
 #include "packed_host.inc"
 #include "kernels_static.inc"
 #include "kernels_middle.inc"
@@ -339,7 +341,7 @@ extern "C" int qcat_kit_describe(const qcat_kit* k, qcat_kit_info* out) {
     if (!k || !out) return set_err(QCAT_ERR_ARG, "qcat_kit_describe: null argument");
     const DevKit& d = k->hk.dk;
     memset(out, 0, sizeof *out);
-    out->packed = (d.fast_ok && packed_supported(d)) ? 1 : 0;
+    out->packed = ((d.fast_ok && packed_supported(d)) || k->hk.simple_packed) ? 1 : 0;
     out->barcode_f16 = d.barcode_f16; out->adapter_f16 = d.adapter_f16;
     out->n_templates = d.nt;
     const int nsets = d.mode == QCAT_MODE_DUAL ? 2 : 1;
@@ -530,6 +532,11 @@ struct qcat_ctx {
     // the handful-of-reads path (kernels_tiny.inc): per read end the templates' (raw, end) and the barcodes' raw scores
     int32_t* tiny_tpl = nullptr; int16_t* tiny_sc = nullptr; size_t cap_tiny = 0, cap_tiny_ends = 0;
     uint32_t last_tiny_ends = 0;                   // read ends the last scan put on that path (0: another path)
+    // simple mode on the packed kernels (kernels_simple.inc): one (key, end) per (work unit, read end); the read ends whose best raw
+    // score is 0 ([0]: their count); debug scans with rows: (raw, end) of every barcode
+    uint2* simple_part = nullptr; size_t cap_simple_part = 0;
+    uint32_t* simple_redo = nullptr; size_t cap_simple_redo = 0;
+    uint32_t* simple_full = nullptr; size_t cap_simple_full = 0;
     // --detect-middle: the reads the packed interior scan leaves (long interiors) on the same kernels (k_midw_*)
     uint32_t* midw_list = nullptr; int32_t* midw_tpl = nullptr; EndRec* midw_recs = nullptr; int16_t* midw_sc = nullptr; size_t cap_midw_sc = 0;
     bool midw_ran = false;
@@ -576,6 +583,7 @@ extern "C" void qcat_ctx_destroy(qcat_ctx* c) {
     if (c->scan_graph.exec) (void)hipGraphExecDestroy(c->scan_graph.exec);
     (void)hipFree(c->win); (void)hipFree(c->wlen); (void)hipFree(c->wspec); (void)hipFree(c->win2); (void)hipFree(c->recs); (void)hipFree(c->results);
     (void)hipFree(c->counts); (void)hipFree(c->dbg_tpl); (void)hipFree(c->dbg_rows); (void)hipFree(c->tiny_tpl); (void)hipFree(c->tiny_sc);
+    (void)hipFree(c->simple_part); (void)hipFree(c->simple_redo); (void)hipFree(c->simple_full);
     (void)hipFree(c->midw_list); (void)hipFree(c->midw_tpl); (void)hipFree(c->midw_recs); (void)hipFree(c->midw_sc);
     (void)hipFree(c->hb_bases); (void)hipFree(c->hb_offsets); (void)hipFree(c->hb_len); (void)hipFree(c->vote_buf);
     packed_scratch_free(&c->packed);
@@ -881,6 +889,52 @@ static int tiny_buffers(qcat_ctx* c, size_t n_ends, int maxb) {
     return 0;
 }
 
+// simple mode on the packed end-tracking kernels (kernels_simple.inc): work units of (tile of 128 read ends, chunk of the list)
+template <int W>
+static void launch_simple_packed(hipStream_t st, KitPtrs kp, const uint8_t* win, const int32_t* wlen, uint32_t n_ends, uint32_t n_tiles,
+                                 int nch, uint2* part, uint32_t* full) {
+    hipLaunchKernelGGL(k_simple_packed<W>, dim3(n_tiles * (uint32_t)nch), dim3(64), 0, st, kp, win, wlen, n_ends, n_tiles, nch, part, full);
+}
+
+static int simple_packed_scan(qcat_ctx* c, KitPtrs kp, const DevKit& hk, size_t n_ends, int16_t* dbg_rows, uint32_t row_stride) {
+    const DevSet& bs = hk.tpl[0].sets[0];
+    const uint32_t n_tiles = (uint32_t)((n_ends + PK_TILE - 1) / PK_TILE);
+    // units: enough of them to fill the chip's wave slots a few times over while the batch is small (a chunk re-stages its
+    // tile's windows, so a big batch takes the list in one piece); `part` holds at most max(tiles, 2 * target) units
+    const uint32_t target = 8192;
+    int nch = (int)std::min<uint32_t>((target + n_tiles - 1) / n_tiles, (uint32_t)bs.n);
+    if (dbg_rows) nch = std::min(nch, 8);
+    const int per = (bs.n + nch - 1) / nch;
+    nch = (bs.n + per - 1) / per;                   // (every chunk holds a barcode)
+    int rc;
+    if (dbg_rows) { if ((rc = grow(&c->simple_full, &c->cap_simple_full, (size_t)n_tiles * bs.n * 128))) return rc; }
+    else {
+        if ((rc = grow(&c->simple_part, &c->cap_simple_part, (size_t)n_tiles * nch * 128))) return rc;
+        if ((rc = grow(&c->simple_redo, &c->cap_simple_redo, n_ends + 1))) return rc;
+        HIPCHK(hipMemsetAsync(c->simple_redo, 0, sizeof(uint32_t), c->stream));
+    }
+    uint32_t* full = dbg_rows ? c->simple_full : nullptr;
+    switch (bs.width) {
+        case 24: launch_simple_packed<24>(c->stream, kp, c->win, c->wlen, (uint32_t)n_ends, n_tiles, nch, c->simple_part, full); break;
+        case 32: launch_simple_packed<32>(c->stream, kp, c->win, c->wlen, (uint32_t)n_ends, n_tiles, nch, c->simple_part, full); break;
+        case 40: launch_simple_packed<40>(c->stream, kp, c->win, c->wlen, (uint32_t)n_ends, n_tiles, nch, c->simple_part, full); break;
+        case 48: launch_simple_packed<48>(c->stream, kp, c->win, c->wlen, (uint32_t)n_ends, n_tiles, nch, c->simple_part, full); break;
+        case 56: launch_simple_packed<56>(c->stream, kp, c->win, c->wlen, (uint32_t)n_ends, n_tiles, nch, c->simple_part, full); break;
+        case 64: launch_simple_packed<64>(c->stream, kp, c->win, c->wlen, (uint32_t)n_ends, n_tiles, nch, c->simple_part, full); break;
+        default: return set_err(QCAT_ERR_UNSUPPORTED, "simple kit without a width class on the packed path");
+    }
+    const uint32_t sblocks = (uint32_t)((n_ends + 255) / 256);
+    if (dbg_rows) {
+        hipLaunchKernelGGL(k_simple_select_rows, dim3(sblocks), dim3(256), 0, c->stream, kp.kit, c->wlen, (uint32_t)n_ends, c->simple_full,
+                           c->recs, dbg_rows, row_stride);
+    } else {
+        hipLaunchKernelGGL(k_simple_select, dim3(sblocks), dim3(256), 0, c->stream, c->wlen, (uint32_t)n_ends, nch, c->simple_part, c->recs, c->simple_redo);
+        const uint32_t rblocks = (uint32_t)std::min<size_t>((n_ends + GEN_THREADS - 1) / GEN_THREADS, 1024);
+        hipLaunchKernelGGL(k_simple_redo, dim3(rblocks), dim3(GEN_THREADS), 0, c->stream, kp, c->win, c->wlen, c->recs, c->simple_redo);
+    }
+    return 0;
+}
+
 // core: scan a resident batch.  dbg: optional debug buffers sized by the caller.
 static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, bool debug, uint32_t row_stride,
                               bool adapter_only = false, int resume_kit_mask = -1, bool keep_counts = false) {
@@ -1008,7 +1062,11 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
     // debug scans keep the records complete for the traces
     const bool slim = use_packed && !debug && hk.mode != QCAT_MODE_SIMPLE && !opt_on(QO_NO_SLIM);
     c->packed.slim = slim;
-    if (hk.mode == QCAT_MODE_SIMPLE) {
+    if (hk.mode == QCAT_MODE_SIMPLE && kit->hk.simple_packed && !c->force_generic && !opt_on(QO_NO_SIMPLE_PACKED)) {
+        // every batch size from one read end up: a chunked packed scan beats one lane walking the whole list
+        if ((rc = simple_packed_scan(c, kp, hk, n_ends, (debug && row_stride) ? c->dbg_rows : nullptr, row_stride))) return rc;
+        mark(c, "k_simple_packed");
+    } else if (hk.mode == QCAT_MODE_SIMPLE) {
         uint32_t blocks = (uint32_t)((n_ends + GEN_THREADS - 1) / GEN_THREADS);
         hipLaunchKernelGGL(k_scan_simple, dim3(blocks), dim3(GEN_THREADS), 0, c->stream, kp, c->win, c->wlen, (uint32_t)n_ends, c->recs,
                            (debug && row_stride) ? c->dbg_rows : nullptr, row_stride);

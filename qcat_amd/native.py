@@ -454,7 +454,7 @@ class NativeKit(object):
         self.jit_thread = None
         from . import jit as jit_mod
         how = {True: "sync", False: "off", None: jit_mod.mode()}[jit]
-        if how == "off":
+        if how == "off" or descriptor.mode == "simple":     # (simple mode: no templates, no static-letter kernels to generate)
             return
         if jit_mod.compiler() is None:
             if jit_mod.needs_code(self.describe()):

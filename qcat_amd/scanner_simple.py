@@ -8,7 +8,11 @@ The reference calls ``find_highest_scoring_barcode(..., compute_identity=True)``
 ``(max_barcode, q_score, max_score, max_end)``: the value ``scan()`` names ``identity`` and compares
 with ``min_quality`` is the normalised *score*, and the ``matches`` / ``length`` statistics never
 leave that function.  So this mode needs exactly what the other modes need from the DP -- score and
-``end_query`` -- and runs on the library's general int32 kernel (``QCAT_MODE_SIMPLE``).
+``end_query``.  A list of one length between 16 and 64 letters (both bundled lists, most FASTA files) runs on
+the library's packed binary16 kernels that track the end position (``csrc/kernels_simple.inc``;
+``NativeKit.describe()["packed"] == 1``); a list of unequal lengths, or one outside those widths, runs on the
+general int32 kernel.  ``qcat --simple`` on a plain FASTQ / FASTA file takes the native file loop
+(``cli._native_demux``) with ``_SimpleLayout`` as its one template.
 """
 import ctypes as C
 import logging
