@@ -39,6 +39,17 @@
 #define ABS_LUT(X, Y, Z, T) qabs::abs_lut_host((X), (Y), (Z), (unsigned)(T))
 #endif
 
+// ABS_PIN2(x, y): an empty asm statement that "rewrites" two registers in place -- no instruction, but the values have to exist
+// where it stands.  The b' planes of a cell are used by the NEXT ROW only, so the compiler is free to sink their last nodes to
+// the end of the row body, and does: every column then keeps the inputs of those nodes alive through the rest of the row
+// (stage 0 of QAB_F1: 140 registers of row state, 229 live at the peak, 98 scratch accesses per row).  Pinned, the state is
+// replaced where the cell stands.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define ABS_PIN2(X, Y) asm volatile("" : "+v"(X), "+v"(Y))
+#else
+#define ABS_PIN2(X, Y) ((void)0)
+#endif
+
 namespace qabs {
 
 typedef uint32_t u32;
@@ -159,6 +170,7 @@ ABS_FN void abs_cell_letter(u32 neq, u32 (&a)[ABS_NP], u32 (&b)[ABS_NP]) {
     const u32 s32 = ABS_LUT(s31, s30, b[3], 0x03);
     a[3] = s25; a[2] = s24; a[1] = s22; a[0] = s20;
     b[3] = s32; b[2] = s30; b[1] = s28; b[0] = s26;
+    ABS_PIN2(b[3], b[2]);                                        // (s30 and s32 feed nothing else in the cell: the nodes that would be sunk)
 }
 
 ABS_FN void abs_cell_n(u32 (&a)[ABS_NP], u32 (&b)[ABS_NP]) {
@@ -190,6 +202,40 @@ ABS_FN void abs_cell_n(u32 (&a)[ABS_NP], u32 (&b)[ABS_NP]) {
     a[3] = s24; a[2] = s22; a[1] = s20; a[0] = s18;
     b[3] = s31; b[2] = s29; b[1] = s27; b[0] = s25;
 }
+
+// ---- the NARROW N cell: two planes of row state per N column ----
+// Claim: in an N column b(i,j) = G(i,j) - G(i,j-1) lies in 0..3 in every row.  There G(i,j) = max(G(i-1,j-1) + 3, G(i-1,j),
+// G(i,j-1)), and each term is bounded against G(i,j-1), by induction over the rows:
+//   * G(i-1,j-1) + 3 <= G(i,j-1) + 3, because G is monotone in i;
+//   * G(i-1,j) = G(i-1,j-1) + b(i-1,j) <= G(i,j-1) + 3 by the hypothesis for row i - 1;
+//   * G(i,j-1) itself gives 0;
+//   * the boundary row has b = 2, and abs_hold2 puts an alignment that has not started back to 2, so the front-padded
+//     form (kernels_abs_mid.inc) starts every alignment inside the bound.
+// With b_in <= 3:  m = max(a_in, b_in, 3) = max(a_in, 3);  b_out = m - a_in = max(3 - a_in, 0) is a function of a_in alone
+// and fits two planes;  a_out = max(a_in, 3) - b_in (four planes in, a two-plane subtrahend) stays in 0..9.  The row state of
+// an N column is therefore b[0], b[1]; the cell neither reads nor writes b[2], b[3] (the kernels do not keep them at all:
+// abs_set2_n / abs_hold2_n / abs_lastrow_step_n are the two-plane forms of what touches a column's row state).
+// Derived by hand as ten nodes (m0 = a0 | ~a3 & ~a2, m1 likewise, a two-plane borrow chain that runs out into a2 and a3,
+// b' = ~a3 & ~a2 & ~a1 / ~a0: the seed of tools/lut3_search_adapter.cpp's mode `2`); the search found the nine-node network
+// below, exact on all 40 valid inputs (a in 0..9, b in 0..3; tests/abs_ncell_check.cpp compares it with abs_cell_n_ref).
+ABS_FN void abs_cell_n2(u32 (&a)[ABS_NP], u32 (&b)[ABS_NP]) {
+    // EXACT=1 narrow N cell, 9 nodes; signals 0..3 = a3..a0, 4..5 = b1..b0; outputs a'3..a'0 b'1..b'0 = s13 s9 s12 s11 s14 s10
+    const u32 s6 = ABS_LUT(a[3], a[2], a[1], 0x83);
+    const u32 s7 = ABS_LUT(a[1], a[0], b[0], 0xd2);
+    const u32 s8 = ABS_LUT(a[1], b[1], s7, 0x4e);
+    const u32 s9 = ABS_LUT(s8, s6, a[3], 0xa1);
+    const u32 s11 = ABS_LUT(a[0], b[0], s6, 0x36);
+    const u32 s12 = ABS_LUT(s6, b[1], s7, 0x36);
+    const u32 s13 = ABS_LUT(s6, s9, a[2], 0xc1);
+    const u32 s10 = ABS_LUT(s6, a[0], s6, 0x28);                 // (b' after the last reader of b: the state is replaced in place)
+    const u32 s14 = ABS_LUT(a[1], s9, s6, 0x82);
+    a[3] = s13; a[2] = s9; a[1] = s12; a[0] = s11;
+    b[1] = s14; b[0] = s10;
+    ABS_PIN2(b[1], b[0]);
+}
+
+ABS_FN void abs_set2_n(u32 (&v)[ABS_NP]) { v[0] = 0u; v[1] = 0xFFFFFFFFu; }
+ABS_FN void abs_hold2_n(u32 (&v)[ABS_NP], u32 hold) { v[0] &= ~hold; v[1] |= hold; }
 
 // mismatch masks of a row against the four letters (codes A, T, G, C = 0..3 in planes c1 c0)
 ABS_FN void abs_neq_masks(u32 c1, u32 c0, u32 (&nq)[4]) {
@@ -289,6 +335,12 @@ ABS_FN void abs_lastrow_init(AbsLastRow& r) {
 ABS_FN void abs_lastrow_step(AbsLastRow& r, const u32 (&b)[ABS_NP], bool first) {
     r.newmax = abs_border_step(r.Fr, b, first ? 0xFFFFFFFFu : 0u);
     abs_accumulate(r.sum, b);
+}
+
+// ... over an N column: its two planes, the upper two are zero (and not kept)
+ABS_FN void abs_lastrow_step_n(AbsLastRow& r, const u32 (&b)[ABS_NP], bool first) {
+    const u32 d[ABS_NP] = {b[0], b[1], 0u, 0u};
+    abs_lastrow_step(r, d, first);
 }
 
 // The decision of oracle/qcat_oracle.c:100-108 for one template, still in planes:

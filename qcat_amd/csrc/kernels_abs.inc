@@ -10,7 +10,7 @@
 //    max_align_length bases): the kernel computes all 2048 slots of a tile and `valid` says which results to keep; the
 //    ordinary 128-end tiles that hold any other window are flagged in `need128` and scanned again by the binary16 kernel
 //    of the same kit (which then skips every tile that is not flagged).
-//  * registers.  The row state is four planes per template column: 240 VGPRs for a 60-column template, 324 for the
+//  * registers.  The row state is four planes per letter column and two per N column (abs_core.h; four everywhere until the narrow N cell): 240 VGPRs for a 60-column template, 324 for the
 //    two templates of PBC096 with their 38 shared columns.  A plan (abs_generated.inc) is therefore cut into TWO stages
 //    that run on the two waves of a workgroup as a software pipeline over blocks of ABS_R rows: wave 0 computes its
 //    columns of block k and hands the difference planes at the cut (and the letters) to wave 1 through a double-buffered
@@ -246,6 +246,30 @@ __device__ __forceinline__ void abs_setprio(int mode, int row, int wg) {
     if (bit) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
 }
 
+// The row state of a stage's columns.  An N column keeps TWO planes (abs_core.h: b stays in 0..3 there; the plan's table
+// N0 / N1, or N of a stage of a four-stage plan, says which columns those are): h[j][2], h[j][3] of such a column are never
+// written nor read, so they take no registers.  S: 0 / 1 = stage of a two-stage plan P, 2 = P is a stage of a four-stage plan.
+template <class P, int S>
+constexpr bool abs_is_n(int j) {
+    if constexpr (S == 0) return P::N0[j] != 0;
+    else if constexpr (S == 1) return P::N1[j] != 0;
+    else return P::N[j] != 0;
+}
+template <class P, int S, int J = 0, int NC>
+__device__ __forceinline__ void abs_set2_cols(u32 (&h)[NC][4]) {
+    if constexpr (J < NC) {
+        if constexpr (abs_is_n<P, S>(J)) qabs::abs_set2_n(h[J]); else qabs::abs_set2(h[J]);
+        abs_set2_cols<P, S, J + 1>(h);
+    }
+}
+template <class P, int S, int J = 0, int NC>
+__device__ __forceinline__ void abs_hold2_cols(u32 (&h)[NC][4], u32 hold) {
+    if constexpr (J < NC) {
+        if constexpr (abs_is_n<P, S>(J)) qabs::abs_hold2_n(h[J], hold); else qabs::abs_hold2(h[J], hold);
+        abs_hold2_cols<P, S, J + 1>(h, hold);
+    }
+}
+
 template <class P>
 __device__ __forceinline__ void abs_body(const AbsArgs& A) {
     using namespace qabs;
@@ -282,8 +306,7 @@ __device__ __forceinline__ void abs_body(const AbsArgs& A) {
                 }
                 blk = 0;
                 if (tile >= 0) {
-#pragma unroll
-                    for (int j = 0; j < P::NC0; ++j) abs_set2(h[j]);
+                    abs_set2_cols<P, 0>(h);
                     src = A.planes + ((size_t)tile * L) * 64 + lane;
 #pragma unroll
                     for (int r = 0; r < ABS_PF; ++r) pf[r] = src[(size_t)min(r, L - 1) * 64];
@@ -338,8 +361,7 @@ __device__ __forceinline__ void abs_body(const AbsArgs& A) {
             if (tile < 0) { __syncthreads(); break; }
             const u32* __restrict__ rb = ring[buf];
             if (blk == 0) {
-#pragma unroll
-                for (int j = 0; j < P::NC1; ++j) abs_set2(h[j]);
+                abs_set2_cols<P, 1>(h);
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -462,8 +484,7 @@ __device__ __forceinline__ void abs_stage(const AbsArgs& A, u32* __restrict__ ri
             break;
         }
         if (blk == 0) {
-#pragma unroll
-            for (int j = 0; j < SS::NC; ++j) abs_set2(h[j]);
+            abs_set2_cols<SS, 2>(h);
 #pragma unroll
             for (int t = 0; t < SS::BD; ++t) {
 #pragma unroll

@@ -9,7 +9,7 @@
 //  * a BIG TILE is 2048 consecutive slots; its row count L is its longest interior, and every other interior is padded at
 //    the FRONT by pad = L - len rows.  Semi-global alignment starts from H(0, j) = 0 whatever came before, so an alignment
 //    that "has not started" simply keeps the boundary state of row 0: after such a row its difference planes are put back
-//    to 2 (abs_hold2, four instructions per column, only in the rows of the tile's padding zone = L - shortest interior:
+//    to 2 (abs_hold2, four instructions per letter column and two per N column, only in the rows of the tile's padding zone = L - shortest interior:
 //    the slots are sorted by length class, so that zone is a few dozen rows of several hundred), its first real row is the
 //    one where the border walk is forced to a new maximum (`first` of abs_border_step, here a per-alignment mask), and its
 //    end position is the tile row minus pad.  Every alignment ends in the tile's last row, so the walk along the last row
@@ -355,8 +355,7 @@ __device__ __forceinline__ void abs_mid_body(const AbsMidArgs& A) {
                 if (tile >= 0) {
                     L = uni(A.t_rows[tile]); pz = uni(A.t_pz[tile]);
                     NB = (L + ABSM_R - 1) / ABSM_R;
-#pragma unroll
-                    for (int j = 0; j < P::NC0; ++j) abs_set2(h[j]);
+                    abs_set2_cols<P, 0>(h);
                     const size_t off = (size_t)(uint32_t)uni((int)A.t_off[tile]);
                     src = A.planes + off * 64 + lane;
                     nsrc = A.ns + off * 64 + lane;
@@ -386,8 +385,7 @@ __device__ __forceinline__ void abs_mid_body(const AbsMidArgs& A) {
                         abs_neq_masks(c.x, c.y, nq);
                         P::row0(nq, h, ho);
                         if (i < pz) {                              // (wave-uniform: the rows in which some alignment of the tile has not started)
-#pragma unroll
-                            for (int j = 0; j < P::NC0; ++j) abs_hold2(h[j], nsm);
+                            abs_hold2_cols<P, 0>(h, nsm);
                             abs_hold2(ho[0], nsm);
                         }
                         u32* __restrict__ row = rb + r * PL * 64 + lane;
@@ -422,8 +420,7 @@ __device__ __forceinline__ void abs_mid_body(const AbsMidArgs& A) {
             if (blk == 0) {
                 L = uni(A.t_rows[tile]); pz = uni(A.t_pz[tile]);
                 NB = (L + ABSM_R - 1) / ABSM_R;
-#pragma unroll
-                for (int j = 0; j < P::NC1; ++j) abs_set2(h[j]);
+                abs_set2_cols<P, 1>(h);
 #pragma unroll
                 for (int q = 0; q < ABS_NF; ++q) bd[0].Fc[q] = 0u;
 #pragma unroll
@@ -446,8 +443,7 @@ __device__ __forceinline__ void abs_mid_body(const AbsMidArgs& A) {
                         prev_ns = nsm;
                         P::row1(nq, h, hi, bd, first, (unsigned)i);
                         if (i < pz) {
-#pragma unroll
-                            for (int j = 0; j < P::NC1; ++j) abs_hold2(h[j], nsm);
+                            abs_hold2_cols<P, 1>(h, nsm);
                         }
                     }
                 }
@@ -518,10 +514,8 @@ __device__ __forceinline__ void abs_mid1_body(const AbsMidArgs& A) {
         const size_t off = (size_t)(uint32_t)uni((int)A.t_off[tile]);
         const uint2* __restrict__ src = A.planes + off * 64 + lane;
         const uint32_t* __restrict__ nsrc = A.ns + off * 64 + lane;
-#pragma unroll
-        for (int j = 0; j < P::NC0; ++j) abs_set2(h0[j]);
-#pragma unroll
-        for (int j = 0; j < P::NC1; ++j) abs_set2(h1[j]);
+        abs_set2_cols<P, 0>(h0);
+        abs_set2_cols<P, 1>(h1);
 #pragma unroll
         for (int q = 0; q < ABS_NF; ++q) bd[0].Fc[q] = 0u;
 #pragma unroll
@@ -549,14 +543,12 @@ __device__ __forceinline__ void abs_mid1_body(const AbsMidArgs& A) {
             const u32 first = prev_ns & ~nsm;                      // the alignments whose first row this is
             prev_ns = nsm;
             if (i < pz) {                                          // (wave-uniform: the rows in which some alignment of the tile has not started)
-#pragma unroll
-                for (int j = 0; j < P::NC0; ++j) abs_hold2(h0[j], nsm);
+                abs_hold2_cols<P, 0>(h0, nsm);
                 abs_hold2(ho[0], nsm);
             }
             P::row1(nq, h1, ho, bd, first, (unsigned)i);
             if (i < pz) {
-#pragma unroll
-                for (int j = 0; j < P::NC1; ++j) abs_hold2(h1[j], nsm);
+                abs_hold2_cols<P, 1>(h1, nsm);
             }
         }
         AbsLastRow lo[1], lr[1];
