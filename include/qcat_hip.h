@@ -410,9 +410,10 @@ int64_t qcat_ctx_graph_replays(const qcat_ctx* ctx);
  * front, ABI 5), out[1] = nominal regions, out[2] = full windows; all zero when the batch was too small for the path.
  * Synchronises the context's stream.  Tests and diagnostics. */
 int qcat_ctx_barcode_bitslice_tiles(qcat_ctx* ctx, uint32_t out[3]);
-/* Read ends the context's latest scan put on the one-wave-per-alignment kernels (csrc/kernels_tiny.inc: batches of a handful of
- * reads -- BarcodeScanner.detect_barcode on one read, qcat/scanner_base.py:521-604); 0: the scan took another path; -1: null
- * context.  Tests and diagnostics. */
+/* What the context's latest call put on the one-wave-per-alignment kernels (csrc/kernels_tiny.inc), counted: the read ends of a
+ * scan of a handful of reads (BarcodeScanner.detect_barcode on one read, qcat/scanner_base.py:521-604), the sequences of
+ * qcat_scan_sequences, the pairs of qcat_sg_align (n without statistics and within QCAT_HIP_WAVE_MAX; 0 with statistics, under QCAT_HIP_NO_TINY=1 and
+ * for gap costs beyond the kernels' range); 0: the call took another path; -1: null context.  Tests and diagnostics. */
 int64_t qcat_ctx_tiny_ends(const qcat_ctx* ctx);
 /* Reads of the context's latest --detect-middle scan (BarcodeScanner.scan_middle inside detect_barcode, qcat/scanner_base.py:479-519,
  * :593-595) whose interior ran on the one-wave-per-alignment kernels: interiors beyond what the packed interior scan takes (more

@@ -13,12 +13,21 @@
 //   k_tiny_barcode  one wave per (read end, set, barcode)   -> tiny_sc[end][set][barcode] = raw
 //   k_tiny_select   one wave per (read end, set)           -> EndRec: rule R2 over the scores in list order
 //
-// then k_finalize as after every other scan kernel.  int32 cells, any 7 x 7 matrix, LINEAR gaps (open == extend: the
-// adapter scoring of every shipped configuration, and the barcode scoring always; with open == extend Gotoh's three
-// matrices collapse to H(i,j) = max(H(i-1,j-1) + W, H(i-1,j) - g, H(i,j-1) - g)).  Same records as k_scan_generic by
+// then k_finalize as after every other scan kernel.  int32 cells, any 7 x 7 matrix.  Read-end scans run LINEAR gaps (open ==
+// extend: the adapter scoring of every shipped configuration, and the barcode scoring always; with open == extend Gotoh's
+// three matrices collapse to H(i,j) = max(H(i-1,j-1) + W, H(i-1,j) - g, H(i,j-1) - g)).  Same records as k_scan_generic by
 // construction -- the decision code IS that kernel's -- and checked against the oracle like every other path
 // (tests/test_tiny_gpu.py: every intermediate through qcat_scan_debug).
+//
+// Whole sequences (qcat_scan_sequences) and plain pairs (qcat_sg_align) use the same wave with every configuration:
+//   k_tiny_adapter_affine   k_tiny_adapter under Gotoh's recurrences (gap_open != gap_extend; the barcode waves stay linear 1/1)
+//   k_tiny_simple_barcode   simple mode: one wave per (sequence, barcode of the list), the barcode's own length -> (raw, end_query)
+//   k_tiny_simple_select    simple mode: one wave per sequence, rule R2 over the normalised scores in list order -> EndRec
+//   k_sg_wave               one wave per (query, target) pair from ASCII, linear or affine, either R1 rule -> qcat_alignment
+// (tests/test_wave_configs_gpu.py; the affine cell on the host: wave_core.h, tests/wave_affine_check.cpp).
 // Included by qcat_hip.hip after kernels_generic.inc.
+
+#include "wave_core.h"
 
 namespace qk {
 
@@ -108,6 +117,59 @@ __device__ inline DevAlign dev_sg_wave(const Q q, int L, const uint8_t* __restri
     return r;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The same wave under Gotoh's recurrences (gap_open != gap_extend) with dev_sg_generic's semantics: F (the gap that consumes
+// query letters) is the same column one step earlier and stays in the lane, E comes from the left neighbour's last step beside
+// h -- one more v_mov_b32_dpp, -inf in front of column 1; column 64 -> 65: one more v_readlane.  A routine of its own, so that
+// the linear one above and every kernel built on it stay exactly the code they were; the column and its cell (wave_core.h)
+// are plain C++ that the host check drives as well.
+// ---------------------------------------------------------------------------------------------------------------------------
+// Calls of the entry points that reach the wave since it took every configuration stay on the general kernels beyond these many
+// alignments (option WAVE_MAX: another limit for all three).  tools/bench_waves.py, profiles/wave_configs_ab.txt: the waves win at
+// every measured size (1 .. 100 000 sequences or pairs; the smallest margin 1.33 x, qcat_sg_align at 100 000 pairs, and falling
+// with n there), so the limits are the largest sizes measured, not a crossover.
+constexpr uint64_t WAVE_SG_MAX = 100000;           // qcat_sg_align without statistics: pairs
+constexpr uint64_t WAVE_AFFINE_MAX = 100000;    // qcat_scan_sequences, gap_open != gap_extend: sequences
+constexpr uint64_t WAVE_SIMPLE_MAX = 12000000;       // qcat_scan_sequences, simple lists: sequences x barcodes
+
+static_assert(WAVE_BIAS == TINY_BIAS, "one bias for both cells");
+
+template <bool TWO /* M > 64 */, class Q>
+__device__ inline DevAlign dev_sg_wave_affine(const Q q, int L, const uint8_t* __restrict__ t, int M, int open, int ext, const int8_t* mat, int lane, bool r1_scalar) {
+    WaveCol a, b;
+    wave_col_init(a, t, lane + 1, M, mat);
+    if (TWO) wave_col_init(b, t, lane + 65, M, mat);
+    int ia = 1 - (lane + 1);
+    int q_cur = lane < L ? q(lane) : 0, q_next = lane + 64 < L ? q(lane + 64) : 0;     // (the query's letters: as dev_sg_wave)
+    for (int d = 2; d <= L + M; ++d) {
+        ++ia;
+        const int r = d - 2;
+        if (r > 0 && (r & 63) == 0) { q_cur = q_next; q_next = r + 64 + lane < L ? q(r + 64 + lane) : 0; }
+        const int first = __builtin_amdgcn_readlane(q_cur, r & 63);
+        int carry_l = 0, carry_h = 0, carry_e = 0;
+        if (TWO) { carry_l = __builtin_amdgcn_readlane(a.letter, 63); carry_h = __builtin_amdgcn_readlane(a.h, 63); carry_e = __builtin_amdgcn_readlane(a.e, 63); }
+        a.letter = tiny_from_left(first, a.letter);
+        const int left_h = tiny_from_left(TINY_BIAS, a.h), left_e = tiny_from_left(WAVE_NEG, a.e);   // H(i, 0) = 0, E(i, 0) = -inf
+        wave_cell_affine(a, left_h, left_e, a.letter, ia, L, open, ext);
+        if (TWO) {
+            b.letter = tiny_from_left(carry_l, b.letter);
+            const int lh = tiny_from_left(carry_h, b.h), le = tiny_from_left(carry_e, b.e);
+            wave_cell_affine(b, lh, le, b.letter, ia - 64, L, open, ext);
+        }
+    }
+    unsigned key = lane + 1 <= M ? ((unsigned)a.row_last << 8) | (unsigned)(255 - lane) : 0u;
+    if (TWO) { const unsigned kb = lane + 65 <= M ? ((unsigned)b.row_last << 8) | (unsigned)(255 - (lane + 64)) : 0u; key = max(key, kb); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) key = max(key, (unsigned)__shfl_xor((int)key, o, 64));
+    DevAlign r;
+    r.score = (int)(key >> 8) - TINY_BIAS; r.end_r = 255 - (int)(key & 255u); r.end_q = L - 1;
+    const int src = (M - 1) & 63;
+    int cmax = __shfl(a.cmax, src, 64), ci = __shfl(a.ci, src, 64);
+    if (TWO && M > 64) { cmax = __shfl(b.cmax, src, 64); ci = __shfl(b.ci, src, 64); }
+    if (cmax > r.score || (cmax == r.score && (r.end_r == M - 1 || r1_scalar))) { r.score = cmax; r.end_r = M - 1; r.end_q = ci - 1; }   // (QCAT_R1_*)
+    return r;
+}
+
 struct TinyArgs {
     KitPtrs kp;
     const uint8_t* win; const int32_t* wlen;       // byte windows (k_pack_windows without the lazy switch)
@@ -148,6 +210,28 @@ k_tiny_adapter(TinyArgs a) {
             r = p.len > 64 ? dev_sg_wave<true>(q, L, tc, p.len, k->gap_open, amat, lane, r1s)
                            : dev_sg_wave<false>(q, L, tc, p.len, k->gap_open, amat, lane, r1s);
         }
+    }
+    if (lane == 0) { a.tpl[((size_t)e * MAX_T + t) * 2] = r.score; a.tpl[((size_t)e * MAX_T + t) * 2 + 1] = r.end_q; }
+}
+
+// the same for a kit whose gap_open != gap_extend, whole sequences only (qcat_scan_sequences: a.seq).  A kernel of its own and
+// not a branch in k_tiny_adapter: that kernel is the latency path of detect_barcode on one read and keeps its code
+__global__ void __launch_bounds__(64)
+k_tiny_adapter_affine(TinyArgs a) {
+    __shared__ int8_t amat[49];
+    const DevKit* k = a.kp.kit;
+    const uint32_t e = blockIdx.x / (uint32_t)k->nt;
+    const int t = (int)(blockIdx.x % (uint32_t)k->nt), lane = (int)threadIdx.x;
+    if (lane < 49) amat[lane] = k->amat[lane];
+    __syncthreads();
+    const int L = tiny_len(a, e);
+    const DevTpl& p = k->tpl[t];
+    DevAlign r; r.score = 0; r.end_q = -1; r.end_r = -1;
+    if (L > 0) {
+        const AsciiSeq q{a.seq + a.seq_off[e]};
+        const uint8_t* tc = a.kp.codes + p.code_off;
+        r = p.len > 64 ? dev_sg_wave_affine<true>(q, L, tc, p.len, k->gap_open, k->gap_extend, amat, lane, k->r1_scalar != 0)
+                       : dev_sg_wave_affine<false>(q, L, tc, p.len, k->gap_open, k->gap_extend, amat, lane, k->r1_scalar != 0);
     }
     if (lane == 0) { a.tpl[((size_t)e * MAX_T + t) * 2] = r.score; a.tpl[((size_t)e * MAX_T + t) * 2 + 1] = r.end_q; }
 }
@@ -248,6 +332,109 @@ k_tiny_store_sequences(TinyArgs a, qcat_result* __restrict__ results) {
     const uint32_t e = blockIdx.x * 64 + threadIdx.x;
     if (e >= a.n_ends) return;
     dev_store_result(results + e, dev_make_scan(a.kp, a.recs[e]), 0, 0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Simple mode on whole sequences (BarcodeScannerSimple.scan, qcat/scanner_simple.py:41-91, as k_scan_sequences runs it): every
+// barcode of the kit's one list against the WHOLE sequence, gaps 1/1, the barcode's own length (a user FASTA may hold barcodes
+// of unequal length), the winners compared by their normalised scores.
+// ---------------------------------------------------------------------------------------------------------------------------
+// grid: (barcode, sequence) -> sc[sequence][barcode] = (raw, end_query).  The end of a barcode alignment is placed in the
+// striped order under either R1 rule (kernels_simple.inc, dev_simple_end: no r1_scalar there).
+__global__ void __launch_bounds__(64)
+k_tiny_simple_barcode(TinyArgs a, int32_t* __restrict__ sc) {
+    __shared__ int8_t bmat[49];
+    const DevKit* k = a.kp.kit;
+    const uint32_t e = blockIdx.y;
+    const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
+    const DevSet& bs = k->tpl[0].sets[0];
+    if (lane < 49) bmat[lane] = k->bmat[lane];
+    __syncthreads();
+    const int L = tiny_len(a, e);
+    const int tl = bs.len_off >= 0 ? a.kp.ids[bs.len_off + 3 * b] : bs.tlen;
+    DevAlign r; r.score = 0; r.end_q = -1; r.end_r = -1;
+    if (L > 0 && tl > 0)                                        // (tl <= QCAT_MAX_TARGET_LEN = 64, kit_prepare.inc: one column per lane)
+        r = dev_sg_wave<false>(AsciiSeq{a.seq + a.seq_off[e]}, L, a.kp.codes + bs.tgt_off + (size_t)b * bs.tlen, tl, 1, bmat, lane, false);
+    if (lane == 0) { sc[((size_t)e * bs.n + b) * 2] = r.score; sc[((size_t)e * bs.n + b) * 2 + 1] = r.end_q; }
+}
+
+// Rule R2 as k_scan_sequences applies it -- the running best replaced when `bi < 0 || braw == 0 || braw * tl < score * blen` --
+// one wave per sequence.  The chain ends at the largest normalised score with the smallest list index among equals unless the
+// largest raw score is exactly 0 (a running best of 0 is replaced by whatever follows): a wave-wide reduction with the
+// cross-multiplied comparison, and lane 0 walks the chain in list order for the sequences whose winner scores 0.
+__global__ void __launch_bounds__(64)
+k_tiny_simple_select(TinyArgs a, const int32_t* __restrict__ sc) {
+    const uint32_t e = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    const DevKit* k = a.kp.kit;
+    const DevSet& bs = k->tpl[0].sets[0];
+    const int L = tiny_len(a, e);
+    int bi = -1, braw = 0, bend = -1;
+    if (L > 0 && bs.n > 0) {
+        const int32_t* s = sc + (size_t)e * bs.n * 2;
+        int blen = 1;
+        for (int b = lane; b < bs.n; b += 64) {                 // ascending: the first index among a lane's equals stays
+            const int v = s[2 * b], tl = bs.len_off >= 0 ? a.kp.ids[bs.len_off + 3 * b] : bs.tlen;
+            if (bi < 0 || braw * tl < v * blen) { bi = b; braw = v; blen = tl; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int oi = __shfl_xor(bi, o, 64), oraw = __shfl_xor(braw, o, 64), olen = __shfl_xor(blen, o, 64);
+            const int lhs = braw * olen, rhs = oraw * blen;      // mine < theirs  <=>  lhs < rhs
+            if (oi >= 0 && (bi < 0 || lhs < rhs || (lhs == rhs && oi < bi))) { bi = oi; braw = oraw; blen = olen; }
+        }
+        if (braw == 0) {                                        // (wave-uniform) the replacement chain, in list order
+            bi = -1; braw = 0; blen = 1;
+            for (int b = 0; b < bs.n; ++b) {
+                const int v = s[2 * b], tl = bs.len_off >= 0 ? a.kp.ids[bs.len_off + 3 * b] : bs.tlen;
+                if (bi < 0 || braw == 0 || braw * tl < v * blen) { bi = b; braw = v; blen = tl; }
+            }
+        }
+        bend = s[2 * bi + 1];
+    }
+    if (lane == 0) {
+        EndRec r;
+        r.window_len = L; r.best_tpl = -1; r.used_tpl = 0; r.best_end = bend; r.best_raw = -1; r.region_path = 0;
+        for (int q = 0; q < 2; ++q) { r.region_start[q] = 0; r.region_len[q] = 0; r.bc_idx[q] = -1; r.bc_raw[q] = 0; }
+        r.region_len[0] = L; r.bc_idx[0] = bi; r.bc_raw[0] = braw;      // (kernels_simple.inc: simple_rec)
+        a.recs[e] = r;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// k_sg_wave: qcat_sg_align without statistics, one wave per (query, target) pair straight from ASCII (k_sg_align's mapping of
+// the letters: X and "other" keep their own codes).  The target's codes are staged in the LDS; linear or Gotoh by the costs
+// (wave-uniform), rule R1 in either order.  Writes what k_sg_align writes for QCAT_STATS_NONE: matches = length = 0, and
+// (0, -1, -1) for an empty query or target.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct AsciiSeqAll {
+    const uint8_t* p;
+    __device__ __forceinline__ int operator()(int i) const { return (int)dev_code_of_ascii(p[i]); }
+};
+
+__global__ void __launch_bounds__(64)
+k_sg_wave(const uint8_t* __restrict__ q, const uint64_t* __restrict__ qoff, const uint8_t* __restrict__ t,
+          const uint64_t* __restrict__ toff, uint32_t n, int open, int ext, SgMatrix mat, int r1_scalar, qcat_alignment* __restrict__ out) {
+    __shared__ uint8_t tc[MAX_TLEN];
+    __shared__ int8_t m[49];
+    const uint32_t a = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    if (a >= n) return;
+    const uint8_t* s2 = t + toff[a];
+    const int L = (int)(qoff[a + 1] - qoff[a]), M = (int)(toff[a + 1] - toff[a]);
+    qcat_alignment r; r.score = 0; r.end_query = -1; r.end_ref = -1; r.matches = 0; r.length = 0;
+    if (L > 0 && M > 0 && M <= MAX_TLEN) {                     // (wave-uniform)
+        if (lane < 49) m[lane] = mat.m[lane];
+        for (int j = lane; j < M; j += 64) tc[j] = dev_code_of_ascii(s2[j]);
+        __syncthreads();
+        const AsciiSeqAll qs{q + qoff[a]};
+        const bool r1s = r1_scalar != 0;
+        DevAlign al;
+        if (open != ext) al = M > 64 ? dev_sg_wave_affine<true>(qs, L, tc, M, open, ext, m, lane, r1s) : dev_sg_wave_affine<false>(qs, L, tc, M, open, ext, m, lane, r1s);
+        else al = M > 64 ? dev_sg_wave<true>(qs, L, tc, M, open, m, lane, r1s) : dev_sg_wave<false>(qs, L, tc, M, open, m, lane, r1s);
+        r.score = al.score; r.end_query = al.end_q; r.end_ref = al.end_r;
+    }
+    if (lane == 0) out[a] = r;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

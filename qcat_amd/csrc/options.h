@@ -55,6 +55,7 @@
     X(NO_SIMPLE_PACKED, "1: simple mode on the general kernel (k_scan_simple) instead of the packed end-tracking kernels") \
     X(NO_TINY, "1: batches of a handful of read ends take the throughput kernels like every other batch") \
     X(TINY_MAX_ENDS, "largest batch (read ends, at most 4096) on the one-wave-per-alignment kernels (default: by the number of alignments, 20000)") \
+    X(WAVE_MAX, "most alignments of a call (pairs of qcat_sg_align without statistics; sequences of qcat_scan_sequences with affine gap costs, sequences x barcodes with a simple list) that take the one-wave kernels (default: the limits in kernels_tiny.inc)") \
     X(AUTO_CHUNK, "batches per call of the kit-auto file loop") \
     X(AUTO_WORKERS, "contexts of the kit-auto file loop") \
     X(NO_GRAPH, "1: host-buffer calls never replay a captured graph") \

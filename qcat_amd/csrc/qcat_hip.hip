@@ -532,6 +532,7 @@ struct qcat_ctx {
     // the handful-of-reads path (kernels_tiny.inc): per read end the templates' (raw, end) and the barcodes' raw scores
     int32_t* tiny_tpl = nullptr; int16_t* tiny_sc = nullptr; size_t cap_tiny = 0, cap_tiny_ends = 0;
     uint32_t last_tiny_ends = 0;                   // read ends the last scan put on that path (0: another path)
+    int32_t* tiny_simple = nullptr; size_t cap_tiny_simple = 0;    // simple kits on qcat_scan_sequences: (raw, end_query) per (sequence, barcode) of a piece
     // simple mode on the packed kernels (kernels_simple.inc): one (key, end) per (work unit, read end); the read ends whose best raw
     // score is 0 ([0]: their count); debug scans with rows: (raw, end) of every barcode
     uint2* simple_part = nullptr; size_t cap_simple_part = 0;
@@ -582,7 +583,7 @@ extern "C" void qcat_ctx_destroy(qcat_ctx* c) {
     if (c->api_graph.exec) (void)hipGraphExecDestroy(c->api_graph.exec);
     if (c->scan_graph.exec) (void)hipGraphExecDestroy(c->scan_graph.exec);
     (void)hipFree(c->win); (void)hipFree(c->wlen); (void)hipFree(c->wspec); (void)hipFree(c->win2); (void)hipFree(c->recs); (void)hipFree(c->results);
-    (void)hipFree(c->counts); (void)hipFree(c->dbg_tpl); (void)hipFree(c->dbg_rows); (void)hipFree(c->tiny_tpl); (void)hipFree(c->tiny_sc);
+    (void)hipFree(c->counts); (void)hipFree(c->dbg_tpl); (void)hipFree(c->dbg_rows); (void)hipFree(c->tiny_tpl); (void)hipFree(c->tiny_sc); (void)hipFree(c->tiny_simple);
     (void)hipFree(c->simple_part); (void)hipFree(c->simple_redo); (void)hipFree(c->simple_full);
     (void)hipFree(c->midw_list); (void)hipFree(c->midw_tpl); (void)hipFree(c->midw_recs); (void)hipFree(c->midw_sc);
     (void)hipFree(c->hb_bases); (void)hipFree(c->hb_offsets); (void)hipFree(c->hb_len); (void)hipFree(c->vote_buf);
@@ -2168,11 +2169,35 @@ extern "C" int qcat_scan_sequences(qcat_ctx* c, const qcat_kit* ckit, const uint
         const DevKit& hk = kit->hk.dk;
         // one wave per alignment along its anti-diagonals (kernels_tiny.inc; round 5): L + M steps per alignment and every
         // template and barcode of a sequence side by side, where the general kernel walks L x M cells of everything on one
-        // lane -- linear gaps and the adapter modes; QCAT_HIP_NO_TINY=1 / simple mode / affine gaps: the general kernel
+        // lane -- every mode: the adapter modes with linear or affine gap costs (k_tiny_adapter / k_tiny_adapter_affine; the
+        // barcode waves are linear 1/1 always), simple mode on k_tiny_simple_*.  QCAT_HIP_NO_TINY=1, the generic switch and gap
+        // costs beyond WAVE_GAP_MAX: the general kernel, as are calls beyond the size limits of kernels_tiny.inc (option WAVE_MAX)
         int maxb = 1;
         for (int t = 0; t < hk.nt; ++t) for (int s2 = 0; s2 < 2; ++s2) maxb = std::max(maxb, (int)hk.tpl[t].sets[s2].n);
-        const bool waves = hk.mode != QCAT_MODE_SIMPLE && hk.gap_open == hk.gap_extend && !opt_on(QO_NO_TINY) && !c->force_generic;
-        if (waves) {
+        const bool affine = hk.gap_open != hk.gap_extend, simple = hk.mode == QCAT_MODE_SIMPLE;
+        const bool gaps_fit = !affine || (hk.gap_open >= 0 && hk.gap_extend >= 0 && hk.gap_open <= WAVE_GAP_MAX && hk.gap_extend <= WAVE_GAP_MAX);
+        // (linear gaps in the adapter modes: every call, as before; the configurations that came later: up to a number of waves)
+        const uint64_t n_waves = simple ? (uint64_t)n_seqs * (uint64_t)std::max(1, (int)hk.tpl[0].sets[0].n)
+                                        : (uint64_t)n_seqs;
+        const bool size_fits = simple ? n_waves <= (uint64_t)opt_val(QO_WAVE_MAX, (int64_t)WAVE_SIMPLE_MAX)
+                                      : !affine || n_waves <= (uint64_t)opt_val(QO_WAVE_MAX, (int64_t)WAVE_AFFINE_MAX);
+        const bool waves = (simple || gaps_fit) && size_fits && !opt_on(QO_NO_TINY) && !c->force_generic;
+        if (waves && simple) {
+            // the scores of a piece: piece x B x 8 bytes, 64 MiB at most (and the grid's y limit as below)
+            const uint32_t nb = (uint32_t)std::max(1, (int)hk.tpl[0].sets[0].n);
+            const uint32_t PIECE = std::max<uint32_t>(1u, std::min<uint32_t>(32767u, (uint32_t)(((size_t)64 << 20) / ((size_t)nb * 8))));
+            const uint32_t piece = std::min(n_seqs, PIECE);
+            rc = grow(&c->recs, &c->cap_recs, (size_t)piece);
+            if (!rc) rc = grow(&c->tiny_simple, &c->cap_tiny_simple, (size_t)piece * nb * 2);
+            for (uint32_t s0 = 0; !rc && s0 < n_seqs; s0 += PIECE) {
+                const uint32_t ns = std::min(PIECE, n_seqs - s0);
+                TinyArgs ta{kp, nullptr, nullptr, b->bases, b->offsets + s0, ns, c->recs, nullptr, nullptr, 0, nullptr, nullptr, 0, 0};
+                if (hk.tpl[0].sets[0].n > 0)
+                    hipLaunchKernelGGL(k_tiny_simple_barcode, dim3(nb, ns), dim3(64), 0, c->stream, ta, c->tiny_simple);
+                hipLaunchKernelGGL(k_tiny_simple_select, dim3(ns), dim3(64), 0, c->stream, ta, (const int32_t*)c->tiny_simple);
+                hipLaunchKernelGGL(k_tiny_store_sequences, dim3((ns + 63) / 64), dim3(64), 0, c->stream, ta, c->results + s0);
+            }
+        } else if (waves) {
             constexpr uint32_t PIECE = 32767;          // (the barcode kernel's grid has (sequence, set) in y: 65535 at most)
             const uint32_t piece = std::min(n_seqs, PIECE);
             rc = grow(&c->recs, &c->cap_recs, (size_t)piece);
@@ -2180,7 +2205,8 @@ extern "C" int qcat_scan_sequences(qcat_ctx* c, const qcat_kit* ckit, const uint
             for (uint32_t s0 = 0; !rc && s0 < n_seqs; s0 += PIECE) {
                 const uint32_t ns = std::min(PIECE, n_seqs - s0);
                 TinyArgs ta{kp, nullptr, nullptr, b->bases, b->offsets + s0, ns, c->recs, c->tiny_tpl, c->tiny_sc, (uint32_t)maxb, nullptr, nullptr, 0, 0};
-                hipLaunchKernelGGL(k_tiny_adapter, dim3(ns * (uint32_t)hk.nt), dim3(64), 0, c->stream, ta);
+                if (affine) hipLaunchKernelGGL(k_tiny_adapter_affine, dim3(ns * (uint32_t)hk.nt), dim3(64), 0, c->stream, ta);
+                else hipLaunchKernelGGL(k_tiny_adapter, dim3(ns * (uint32_t)hk.nt), dim3(64), 0, c->stream, ta);
                 hipLaunchKernelGGL(k_tiny_decide, dim3((ns + 63) / 64), dim3(64), 0, c->stream, ta);
                 hipLaunchKernelGGL(k_tiny_barcode, dim3((uint32_t)maxb, ns * 2), dim3(64), 0, c->stream, ta);
                 hipLaunchKernelGGL(k_tiny_select, dim3(ns * 2), dim3(64), 0, c->stream, ta);
@@ -2217,22 +2243,34 @@ extern "C" int qcat_sg_align(qcat_ctx* c, const uint8_t* queries, const uint64_t
     HIPCHK(hipSetDevice(c->device));
     const uint64_t qb = q_offsets[n], tb = t_offsets[n];
     if ((qb && !queries) || (tb && !targets)) return set_err(QCAT_ERR_ARG, "qcat_sg_align: null sequence buffer");
+    // without statistics: one wave per pair along its anti-diagonals (kernels_tiny.inc: k_sg_wave), no scratch; the statistics
+    // need the matrices of the traceback and stay on k_sg_align, as do QCAT_HIP_NO_TINY=1, the generic switch and gap costs
+    // beyond WAVE_GAP_MAX and calls of more than WAVE_SG_MAX pairs (option WAVE_MAX)
+    const bool waves = with_stats == QCAT_STATS_NONE && !opt_on(QO_NO_TINY) && !c->force_generic &&
+                       gap_open <= WAVE_GAP_MAX && gap_extend <= WAVE_GAP_MAX && (uint64_t)n <= (uint64_t)opt_val(QO_WAVE_MAX, (int64_t)WAVE_SG_MAX);
+    c->last_tiny_ends = 0;
     const uint32_t blocks = (n + GEN_THREADS - 1) / GEN_THREADS;
     const size_t threads = (size_t)blocks * GEN_THREADS;
     DevTemp dq, dqo, dt, dto, dscr, dout;
     HIPCHK(dq.alloc(qb + 1)); HIPCHK(dqo.alloc(((size_t)n + 1) * 8)); HIPCHK(dt.alloc(tb + 1)); HIPCHK(dto.alloc(((size_t)n + 1) * 8));
-    HIPCHK(dscr.alloc((with_stats ? 6 : 2) * (size_t)(MAX_TLEN + 1) * threads * 4)); HIPCHK(dout.alloc((size_t)n * sizeof(qcat_alignment)));
+    if (!waves) HIPCHK(dscr.alloc((with_stats ? 6 : 2) * (size_t)(MAX_TLEN + 1) * threads * 4));
+    HIPCHK(dout.alloc((size_t)n * sizeof(qcat_alignment)));
     if (qb) HIPCHK(hipMemcpyAsync(dq.p, queries, qb, hipMemcpyHostToDevice, c->stream));
     if (tb) HIPCHK(hipMemcpyAsync(dt.p, targets, tb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(dqo.p, q_offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(dto.p, t_offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     SgMatrix m;
     memcpy(m.m, matrix, 49);
+    if (waves)
+        hipLaunchKernelGGL(k_sg_wave, dim3(n), dim3(64), 0, c->stream, dq.as<uint8_t>(), dqo.as<uint64_t>(), dt.as<uint8_t>(),
+                           dto.as<uint64_t>(), n, (int)gap_open, (int)gap_extend, m, (int)(r1_flag != 0), dout.as<qcat_alignment>());
+    else
     hipLaunchKernelGGL(k_sg_align, dim3(blocks), dim3(GEN_THREADS), 0, c->stream, dq.as<uint8_t>(), dqo.as<uint64_t>(), dt.as<uint8_t>(),
                        dto.as<uint64_t>(), n, (int)gap_open, (int)gap_extend, m, (int)(with_stats | r1_flag), dscr.as<int32_t>(), dout.as<qcat_alignment>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(qcat_alignment), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    c->last_tiny_ends = waves ? n : 0;
     return 0;
 }
 
