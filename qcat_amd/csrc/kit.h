@@ -82,7 +82,7 @@ struct DevSet {
 constexpr int BS_C_MIN = 20, BS_C_MAX = 48;    // own columns (tlen - bs_pre - bs_post) the bit-sliced kernels are instantiated for
 constexpr int BS_MAX_TARGET = 63;              // columns of a target on the bit-sliced kernels: a score counter holds H + 64 in [0, 127] (bs_core.h) and
                                                // a target matched letter for letter scores its length (the rule is restated beside bs_post_of's)
-// trailing columns of a set on the bit-sliced kernels (the rule is restated in tools/gen_static_kernels.py and qcat_amd/jit.py)
+// trailing columns of a set on the bit-sliced kernels (the rule is restated once in Python: qcat_amd/static_text.py, bs_shape)
 inline int bs_post_of(int trail, int tlen, int pre) {
     const int posts[5] = {11, 8, 7, 6, 4};
     for (int q : posts) if (q <= trail && tlen - pre - q >= BS_C_MIN) return q;

@@ -2,7 +2,9 @@
 
 The library ships generated column chains for every template and barcode target of
 ``resources/kits.json`` (``csrc/static_generated.inc``); a custom kit (``--kit-folder``) would
-otherwise run the slower table kernels.  This module emits the same chains for ONE kit descriptor,
+otherwise run the slower table kernels.  This module emits the same structs for ONE kit descriptor (their
+text comes from ``static_text.py``, the module ``tools/gen_static_kernels.py`` writes the built-in kits with; decided
+here: which barcodes form a pair, a quad and a case, and the entry points),
 compiles them IN PROCESS with hipRTC (``libhiprtc``, against the device-only ``csrc/rtc_prelude.inc``;
 ``hipcc --genco`` against ``csrc/jit_prelude.inc`` is the fall-back when the hipRTC library is
 missing) and hands the code object to the library (``qcat_kit_attach_code``).
@@ -32,13 +34,14 @@ import tempfile
 import threading
 
 from . import abs_plan
+from . import static_text as st
 from .codes import ASCII_TO_CODE
+from .static_text import BS_C_MAX, BS_C_MIN, BS_MAX_TARGET, QUAD_MIN_TARGETS  # noqa: F401
+from .static_text import bs_shape as _bs_shape
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 ARCH = "gfx950"
 MAX_TEMPLATES = 16
-QUAD_MIN_TARGETS = 48            # as tools/gen_static_kernels.py: sets this large also get four-target chains
-_LETTER = {0: 0, 1: 1, 2: 2, 3: 3, 4: 4}          # code -> E[] index: A, T, G, C (+ N in templates)
 
 
 def mode():
@@ -108,34 +111,11 @@ def _codes(seq):
     return [int(ASCII_TO_CODE[ord(c)]) for c in seq]
 
 
-def _chain(codes):
-    """the column chain of tools/gen_static_kernels.py: chunks of four, the next chunk's diagonal term
-    formed before the current chunk's writes"""
-    e = ["E[%d]" % _LETTER[c] for c in codes]
-    out = ["QS_BEGIN(%s)" % e[0]]
-    n = len(codes)
-    for j in range(0, n, 4):
-        k = min(4, n - j)
-        inner = e[j + 1:j + k]
-        if j + k < n:
-            out.append("QS_CHUNK4(%d, %s)" % (j + 1, ", ".join(inner + [e[j + k]])))
-        else:
-            out.append("QS_LAST%d(%d%s)" % (k, j + 1, "".join(", " + x for x in inner)))
-    return " ".join(out)
-
-
-def _lcp(a, b):
-    n = 0
-    while n < len(a) and n < len(b) and a[n] == b[n]:
-        n += 1
-    return n
-
-
 def _pair_up(targets, flank):
     """greedy pairing of the set's targets by longest common prefix (two targets run in one row pass
     and share their common prefix columns): [(barcode a, barcode b or -1, shared columns)]"""
     idx = range(len(targets))
-    cand = sorted(((-_lcp(targets[i], targets[j]), i, j) for i in idx for j in idx if i < j))
+    cand = sorted(((-st.lcp(targets[i], targets[j]), i, j) for i in idx for j in idx if i < j))
     used, pairs = set(), []
     for neg, i, j in cand:
         if i in used or j in used or targets[i] == targets[j]:
@@ -187,7 +167,7 @@ def _abs_plans(t, sequence):
 
 
 def generate(descriptor, skip_templates=(), skip_groups=()):
-    """(source text, template flags, group flags, pair entries per group) for the templates /
+    """(source text, template flags, group flags, pair entries per group, quads per group) for the templates /
     (template, set) groups of ``descriptor`` that can take static-letter kernels and are not in the
     skip lists"""
     n = int(descriptor.desc.barcode_context_length)
@@ -199,13 +179,12 @@ def generate(descriptor, skip_templates=(), skip_groups=()):
     abs_text = []                                            # bit-sliced adapter plans (namespace qabs, after namespace qk)
     abs_ok = _abs_ok(descriptor) and os.environ.get("QCAT_AMD_JIT_NO_ABS") is None
     entries = [[] for _ in range(2 * MAX_TEMPLATES)]          # per group: (pair case, barcode a, barcode b or -1)
-    quads = [[] for _ in range(2 * MAX_TEMPLATES)]            # per group: (quad case, barcodes a, b, c, d, shared column counts)
+    quads = [[] for _ in range(2 * MAX_TEMPLATES)]            # per group: (quad case, barcodes a, b, c, d)
     for t, lay in enumerate(descriptor.layouts):
         tcodes = _codes(lay.sequence)
         if t not in skip_templates and all(c <= 4 for c in tcodes) and 1 <= len(tcodes) <= 128:
             m = len(tcodes)
-            parts.append("struct QACJ_%d { static __device__ __forceinline__ void run(h2 (&h)[%d], h2& carry, h2& left, "
-                         "const h2 (&E)[5]) { %s } };\n" % (t, m + 1, _chain(tcodes)))
+            parts.append(st.adapter_chain_struct("QACJ_%d" % t, tcodes))
             entry.append('extern "C" __global__ void __launch_bounds__(qk::PK_WAVES * 64, QS_ADAPTER_WAVES(%d)) '
                          "qj_ad_%d(qk::StaticAdapterArgs a) { qk::adapter_static_body<%d, qk::QACJ_%d>(a); }\n" % (m, t, m, t))
             entry.append('extern "C" __global__ void __launch_bounds__(qk::PK_WAVES * 64, QS_ADAPTER_WAVES(%d)) '
@@ -240,43 +219,21 @@ def generate(descriptor, skip_templates=(), skip_groups=()):
                 quad_list = [(full[i], full[i + 1]) for i in range(0, len(full), 2)]
             else:
                 left = pairs
-            for qd, ((a1, a2, ua), (b1, b2, ub)) in enumerate(quad_list):
-                t1, t2, t3, t4 = targets[a1], targets[a2], targets[b1], targets[b2]
-                u0 = min(_lcp(t1, t3), ua, ub)
-                parts.append("struct QSQJ_%d_%d {\n" % (g, qd))
-                parts.append("    static __device__ __forceinline__ void pre0(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[4]) { %s }\n"
-                             % (u0 + 1, _chain(t1[:u0]) if u0 else ""))
-                for name, tg, lo, hi in (("prea", t1, u0, ua), ("ta", t1, ua, m), ("tb", t2, ua, m),
-                                         ("preb", t3, u0, ub), ("tc", t3, ub, m), ("td", t4, ub, m)):
-                    parts.append("    static __device__ __forceinline__ void %s(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[4]) { %s }\n"
-                                 % (name, hi - lo + 1, _chain(tg[lo:hi]) if hi > lo else ""))
-                parts.append("};\n")
-                quads[g].append((qd, a1, a2, b1, b2, u0, ua - u0, ub - u0))
-            for pr, (ba, bb, up_) in enumerate(left):
-                ta, tb = targets[ba], targets[bb if bb >= 0 else ba]
-                parts.append("struct QSPJ_%d_%d {\n" % (g, pr))
-                parts.append("    static __device__ __forceinline__ void pre(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[4]) { %s }\n"
-                             % (up_ + 1, _chain(ta[:up_]) if up_ else ""))
-                for name, tg in (("ta", ta), ("tb", tb)):
-                    parts.append("    static __device__ __forceinline__ void %s(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[4]) { %s }\n"
-                                 % (name, m - up_ + 1, _chain(tg[up_:])))
-                parts.append("};\n")
-                entries[g].append((pr, ba, bb))
-            parts.append("struct QSGJ_%d {\n    static constexpr int M = %d;\n    static constexpr int HAS_QUADS = %d;\n"
-                         "    static __device__ __forceinline__ void run4(int quad, const uint8_t* qbuf, int lane, int Lmax, h2 gL2, "
-                         "u32 special, const u32 (&ltr)[4], h2 rowoff, h2 coloff, u32& ra, u32& rb, u32& rc, u32& rd) {\n"
-                         "        ra = 0; rb = 0; rc = 0; rd = 0;\n        switch (quad) {\n" % (g, m, 1 if quad_list else 0))
-            for qd, a1, a2, b1, b2, u0, da, db in quads[g]:
-                parts.append("        case %d: static_barcode_rows4<M, %d, %d, %d, QSQJ_%d_%d>(qbuf, lane, Lmax, gL2, special, ltr, rowoff, coloff, ra, rb, rc, rd); break;\n"
-                             % (qd, u0, da, db, g, qd))
-            parts.append("        default: break;\n        }\n    }\n"
-                         "    static __device__ __forceinline__ void run(int pair, const uint8_t* qbuf, int lane, int Lmax, h2 gL2, "
-                         "u32 special, const u32 (&ltr)[4], h2 rowoff, h2 coloff, u32& ra, u32& rb) {\n        ra = 0; rb = 0;\n"
-                         "        switch (pair) {\n")
-            for pr, (ba, bb, up_) in enumerate(left):
-                parts.append("        case %d: static_barcode_rows2<M, %d, QSPJ_%d_%d>(qbuf, lane, Lmax, gL2, special, ltr, rowoff, coloff, ra, rb); break;\n"
-                             % (pr, up_, g, pr))
-            parts.append("        default: break;\n        }\n    }\n};\n")
+            def chains(pair):                                # (target a, target b, shared columns); alone: paired with itself
+                return targets[pair[0]], targets[pair[1] if pair[1] >= 0 else pair[0]], pair[2]
+
+            quad_cases = []                                  # (quad struct, columns all four share, + pair a, + pair b)
+            for qd, (pa, pb) in enumerate(quad_list):
+                ca, cb = chains(pa), chains(pb)
+                u0 = st.quad_shared(ca, cb)
+                parts.append(st.quad_struct("QSQJ_%d_%d" % (g, qd), ca, cb, u0))
+                quad_cases.append(("QSQJ_%d_%d" % (g, qd), u0, pa[2] - u0, pb[2] - u0))
+                quads[g].append((qd, pa[0], pa[1], pb[0], pb[1]))
+            for pr, pair in enumerate(left):
+                parts.append(st.pair_struct("QSPJ_%d_%d" % (g, pr), *chains(pair)))
+                entries[g].append((pr, pair[0], pair[1]))
+            parts.append(st.group_struct("QSGJ_%d" % g, m, quad_cases,
+                                         [("QSPJ_%d_%d" % (g, pr), pair[2]) for pr, pair in enumerate(left)]))
             entry.append('extern "C" __global__ void __launch_bounds__(qk::PK_WAVES * 64, %d) '
                          "qj_bc_%d(qk::StaticArgs a) { qk::barcode_static_body<qk::QSGJ_%d>(a); }\n" % (2 if quad_list else 4, g, g))
             grp_flags[g] = 1
@@ -285,17 +242,7 @@ def generate(descriptor, skip_templates=(), skip_groups=()):
             # their letters from memory)
             shape = _bs_shape(len(up), len(dn), m) if len(targets) <= 128 and os.environ.get("QCAT_AMD_JIT_NO_BS") is None else None
             if shape:
-                rev, pre, own, post = shape
-                s1, s0 = _bs_shared_words(targets[0], rev, pre)
-                t1, t0 = _bs_trailing_words(targets[0], rev, post)
-                parts.append("struct QBSJ_%d {\n    static constexpr int C = %d, KERNEL = QCAT_JIT_BASE + %d, PRE = %d, POST = %d;\n"
-                             "    static constexpr unsigned S1 = 0x%Xu, S0 = 0x%Xu, T1 = 0x%Xu, T0 = 0x%Xu;\n"
-                             "    static __device__ __forceinline__ void rows(int kase, const BsRowArgs& ra, "
-                             "u32 (&h1)[C], u32 (&h0)[C], u32 (&f)[BS_ND]) {\n        switch (kase) {\n" % (g, own, g, pre, post, s1, s0, t1, t0))
-                for b, tg in enumerate(targets):
-                    w1, w0 = _bs_words(tg, rev, pre, own)
-                    parts.append("        case %d: bs_rows_static<C, PRE != 0, 0x%XULL, 0x%XULL>(ra, h1, h0, f); break;\n" % (b, w1, w0))
-                parts.append("        default: break;\n        }\n    }\n};\n")
+                parts.append(st.bs_row_struct("QBSJ_%d" % g, "QCAT_JIT_BASE + %d" % g, shape, list(enumerate(targets))))
                 entry.append('extern "C" __global__ void __launch_bounds__(qk::BS_WAVES * 64) '
                              "qj_bs_%d(qk::BsArgs a) { qk::bs_barcode_body<qk::QBSJ_%d>(a); }\n" % (g, g))
                 grp_flags[g] |= 2
@@ -305,59 +252,7 @@ def generate(descriptor, skip_templates=(), skip_groups=()):
         parts.append('#define QCAT_ABS_NO_BUILTIN 1\n#include "kernels_abs.inc"\n'
                      "#define ABS_COPY4(D, S) do { (D)[0] = (S)[0]; (D)[1] = (S)[1]; (D)[2] = (S)[2]; (D)[3] = (S)[3]; } while (0)\n"
                      "namespace qabs {\n" + "".join(abs_text) + "}  // namespace qabs\n")
-    return "".join(parts + entry), tpl_flags, grp_flags, entries, [[q[:5] for q in g] for g in quads]
-
-
-BS_C_MIN, BS_C_MAX = 20, 48          # kit.h
-
-
-BS_POSTS = (11, 8, 7, 6, 4)          # kit.h: bs_post_of
-BS_MAX_TARGET = 63                   # kit.h: a 64-column target read without an error scores 64, beyond the counters' planes
-
-
-def _bs_shape(uplen, downlen, m):
-    """(reversed, shared columns, own columns, trailing columns) of a set on the bit-sliced kernels, or None -- the rule of
-    kit_prepare.inc: the longer context leads, 11 / 8 / 4 / 0 of its columns are shared; 11 / 8 / 7 / 6 / 4 / 0 columns of the
-    other context go through the reversed DP (csrc/bs_core.h)"""
-    rev = downlen > uplen
-    lead, trail = (downlen, uplen) if rev else (uplen, downlen)
-    pre = 11 if lead >= 11 else (8 if lead >= 8 else (4 if lead >= 4 else 0))
-    post = next((q for q in BS_POSTS if q <= trail and m - pre - q >= BS_C_MIN), 0)
-    own = m - pre - post
-    if not (BS_C_MIN <= own <= BS_C_MAX and m <= BS_MAX_TARGET):
-        return None
-    return rev, pre, own, post
-
-
-def _bs_words(codes, rev, pre, own):
-    """letter bit words of the own columns in the order the kernel walks them (bit j = own column j)"""
-    t = codes[::-1] if rev else codes
-    w1 = w0 = 0
-    for j, c in enumerate(t[pre:pre + own]):
-        w1 |= ((c >> 1) & 1) << j
-        w0 |= (c & 1) << j
-    return w1, w0
-
-
-def _bs_trailing_words(codes, rev, post):
-    """letter bit words of the trailing columns in the order the reversed DP walks them (bit j = the last column but j)"""
-    t = codes[::-1] if rev else codes
-    w1 = w0 = 0
-    for j in range(post):
-        c = t[len(t) - 1 - j]
-        w1 |= ((c >> 1) & 1) << j
-        w0 |= (c & 1) << j
-    return w1, w0
-
-
-def _bs_shared_words(codes, rev, pre):
-    """letter bit words of the shared (leading context) columns: bit j = shared column j"""
-    t = codes[::-1] if rev else codes
-    w1 = w0 = 0
-    for j, c in enumerate(t[:pre]):
-        w1 |= ((c >> 1) & 1) << j
-        w0 |= (c & 1) << j
-    return w1, w0
+    return "".join(parts + entry), tpl_flags, grp_flags, entries, quads
 
 
 def _prelude_digest():

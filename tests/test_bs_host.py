@@ -73,18 +73,19 @@ def test_bit_sliced_barcode_arithmetic_equals_the_oracle_dp(host_check, tmp_path
 
 def test_the_longest_target_the_counters_hold(host_check, tmp_path):
     """a score counter holds H + 64 in [0, 127] (bs_core.h) and a target read without an error scores its length: 63 columns
-    are the most the bit-sliced kernels can take (kit.h BS_MAX_TARGET; kit_prepare.inc, jit._bs_shape and the generator's
-    bs_shape leave a 64-column set on the binary16 kernels).  Found by the kit-geometry sweep: custom kits with targets of 64
+    are the most the bit-sliced kernels can take (kit.h BS_MAX_TARGET; kit_prepare.inc and static_text.bs_shape -- the one
+    rule behind jit._bs_shape and the generator's bs_shape -- leave a 64-column set on the binary16 kernels).  Found by the kit-geometry sweep: custom kits with targets of 64
     columns lost every perfect read on the bit-sliced path (64 wraps).  63 columns in both directions, split and unsplit,
     against the oracle's DP -- the batches of the host check hold error-free regions"""
     import gen_static_kernels as g
-    from qcat_amd import jit
+    from qcat_amd import jit, static_text
+    assert g.bs_shape is static_text.bs_shape is jit._bs_shape
     rng = random.Random(63)
     lines = []
     for uplen, dnlen in ((11, 4), (6, 11), (11, 11)):
-        assert g.bs_shape(uplen, dnlen, 64) is None and jit._bs_shape(uplen, dnlen, 64) is None
+        assert g.bs_shape(uplen, dnlen, 64) is None
         shape = g.bs_shape(uplen, dnlen, 63)
-        assert shape is not None and shape == jit._bs_shape(uplen, dnlen, 63)
+        assert shape is not None
         up = "".join(rng.choice("ACGT") for _ in range(uplen))
         dn = "".join(rng.choice("ACGT") for _ in range(dnlen))
         targets = [up + "".join(rng.choice("ACGT") for _ in range(63 - uplen - dnlen)) + dn for _ in range(6)]

@@ -33,10 +33,12 @@ def test_generated_source_is_in_sync_with_the_kit_bundle():
     assert open(gen.OUT).read() == text, "run python tools/gen_static_kernels.py"
     assert open(gen.BS_OUT).read() == bs_text, "run python tools/gen_static_kernels.py"
     assert n_kernels >= 16 and n_targets >= 600 and n_templates >= 14
-    # no shipped target family is longer than the bit-sliced kernels' score counters hold (kit.h BS_MAX_TARGET, restated in the
-    # generator and in qcat_amd/jit.py): the limit leaves the generated files as they were
-    from qcat_amd import jit
-    assert gen.BS_MAX_TARGET == jit.BS_MAX_TARGET == 63 and max(m for _, _, m in gen.collect()[0]) < 63
+    # no shipped target family is longer than the bit-sliced kernels' score counters hold (kit.h BS_MAX_TARGET, restated once in
+    # Python: generator and qcat_amd/jit.py both take it, and the shape rule, from qcat_amd/static_text.py): the limit leaves
+    # the generated files as they were
+    from qcat_amd import jit, static_text
+    assert gen.bs_shape is static_text.bs_shape is jit._bs_shape
+    assert gen.BS_MAX_TARGET == jit.BS_MAX_TARGET == static_text.BS_MAX_TARGET == 63 and max(m for _, _, m in gen.collect()[0]) < 63
 
 
 @pytest.mark.parametrize("mode", ["epi2me", "dual"])

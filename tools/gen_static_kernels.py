@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Generate qcat_amd/csrc/static_generated.inc: barcode column chains with compile-time target
-letters for every barcode target of the built-in kits (see kernels_static.inc).
+"""Generate qcat_amd/csrc/static_generated.inc and bs_static_generated.inc: barcode column chains and bit-sliced rows with
+compile-time target letters for every barcode target of the built-in kits (see kernels_static.inc, kernels_bitslice.inc).
 
 A *target* is upstream context + barcode + downstream context exactly as the scanners build it
 (qcat_amd.layout.AdapterLayout, mirroring qcat/layout.py:191-238) with the default
 barcode_context_length.  Targets that share both flanks form one *family* = one kernel; a kit group
 (template, set) can use the kernel when all of its targets are cases of the same family, which the
 library checks at kit creation through the registry (FNV-1a 64 of the target codes -> kernel, case).
+
+The text of every struct, the shape rule of the bit-sliced rows and their constants come from qcat_amd/static_text.py,
+which qcat_amd/jit.py uses for custom kits; this file decides what is a family, a pair, a quad and a case, and writes
+the registries, the launch switches and the merged kernels around the structs.
 
 Run from the repo root:  python tools/gen_static_kernels.py
 """
@@ -19,17 +23,19 @@ sys.path.insert(0, ROOT)
 
 from qcat_amd import config as qconfig          # noqa: E402
 from qcat_amd import scanner                    # noqa: E402
+from qcat_amd import static_text as st          # noqa: E402
+from qcat_amd.static_text import BS_C_MAX, BS_C_MIN, BS_MAX_TARGET, BS_POSTS, QUAD_MIN_TARGETS, bs_shape  # noqa: E402,F401
 
 OUT = os.path.join(ROOT, "qcat_amd", "csrc", "static_generated.inc")
-QUAD_MIN_TARGETS = 48       # families this large also get four-target chains (the big sets dominate the run time)
 BS_MIN_TARGETS = 12         # families this large get bit-sliced row loops with the letters compiled in (kernels_bitslice.inc)
-BS_C_MIN, BS_C_MAX = 20, 48 # kit.h
-BS_POSTS = (11, 8, 7, 6, 4) # trailing columns the reversed DP takes (kit_prepare.inc, the instantiations of kernels_bitslice.inc)
-BS_MAX_TARGET = 63          # kit.h: a score counter holds up to 63 and a target read without an error scores its length
 BS_PARTS = 6                # translation units the bit-sliced static-letter kernels are split over (__graft_entry__.build)
 BS_OUT = os.path.join(ROOT, "qcat_amd", "csrc", "bs_static_generated.inc")
 CODE = {"A": 0, "T": 1, "G": 2, "C": 3}
 ACODE = {"A": 0, "T": 1, "G": 2, "C": 3, "N": 4}        # adapter templates also hold barcode placeholders
+
+
+def _codes(seq):
+    return [ACODE[c] for c in seq]
 
 
 def fnv1a64(codes):
@@ -40,79 +46,12 @@ def fnv1a64(codes):
     return h
 
 
-def chain(letters, code):
-    """column chain in chunks of four.  Every read of the previous row happens before the chunk's
-    first write and the diagonal term of the NEXT chunk's first column is formed inside this chunk,
-    so h[] is updated in place: no old h[j] outlives its new value, no register copies at the loop
-    back edge."""
-    e = ["E[%d]" % code[c] for c in letters]
-    out = ["QS_BEGIN(%s)" % e[0]]
-    n = len(letters)
-    for j in range(0, n, 4):
-        k = min(4, n - j)
-        inner = e[j + 1:j + k]
-        if j + k < n:
-            out.append("QS_CHUNK4(%d, %s)" % (j + 1, ", ".join(inner + [e[j + k]])))
-        else:
-            out.append("QS_LAST%d(%d%s)" % (k, j + 1, "".join(", " + x for x in inner)))
-    return " ".join(out)
-
-
-def bs_shape(uplen, downlen, m):
-    """(reversed, shared columns, own columns, trailing columns) of a target family on the bit-sliced kernels, or None: the
-    rule of kit_prepare.inc (the longer context leads; 11 / 8 / 4 / 0 of its columns are shared; round 5: the other context's
-    columns -- 11 / 8 / 7 / 6 / 4 / 0 of them, as long as BS_C_MIN own columns remain -- are computed once per super-tile as well, by
-    the reversed DP of bs_core.h)"""
-    rev = downlen > uplen
-    lead, trail = (downlen, uplen) if rev else (uplen, downlen)
-    pre = 11 if lead >= 11 else (8 if lead >= 8 else (4 if lead >= 4 else 0))
-    post = next((q for q in BS_POSTS if q <= trail and m - pre - q >= BS_C_MIN), 0)
-    own = m - pre - post
-    if not (BS_C_MIN <= own <= BS_C_MAX and m <= BS_MAX_TARGET):
-        return None
-    return rev, pre, own, post
-
-
-def bs_words(target, rev, pre, code, own=None):
-    """letter bit words of the own columns in the order the kernel walks them (bit j = own column j)"""
-    t = target[::-1] if rev else target
-    w1 = w0 = 0
-    for j, ch in enumerate(t[pre:pre + own] if own is not None else t[pre:]):
-        c = code[ch]
-        w1 |= ((c >> 1) & 1) << j
-        w0 |= (c & 1) << j
-    return w1, w0
-
-
-def bs_trailing_words(target, rev, post, code):
-    """letter bit words of the trailing context's columns in the order the REVERSED DP walks them (bit j = its column j =
-    the target's last column but j, in walk order)"""
-    t = target[::-1] if rev else target
-    w1 = w0 = 0
-    for j in range(post):
-        c = code[t[len(t) - 1 - j]]
-        w1 |= ((c >> 1) & 1) << j
-        w0 |= (c & 1) << j
-    return w1, w0
-
-
-def bs_shared_words(target, rev, pre, code):
-    """letter bit words of the shared (leading context) columns: bit j = shared column j"""
-    t = target[::-1] if rev else target
-    w1 = w0 = 0
-    for j, ch in enumerate(t[:pre]):
-        c = code[ch]
-        w1 |= ((c >> 1) & 1) << j
-        w0 |= (c & 1) << j
-    return w1, w0
-
-
 def pair_up(targets, flank):
     """greedy pairing by longest common prefix: [(ta, tb, shared columns)]; a leftover target is paired
     with itself.  Two targets that run in one row pass share their common prefix columns, so the
     longer the prefix the fewer columns a pair costs (static_barcode_rows2)."""
     rem = list(targets)
-    cand = sorted(((len(os.path.commonprefix([a, b])), a, b) for i, a in enumerate(rem) for b in rem[i + 1:]),
+    cand = sorted(((st.lcp(a, b), a, b) for i, a in enumerate(rem) for b in rem[i + 1:]),
                   key=lambda x: (-x[0], x[1], x[2]))
     used, pairs = set(), []
     for lcp, a, b in cand:
@@ -145,7 +84,7 @@ def collect():
                 by_kit.setdefault(lay.kit, []).append(lay.sequence.upper())
             for seqs in by_kit.values():
                 if len(seqs) == 2 and all(c in ACODE for q in seqs for c in q):
-                    u = len(os.path.commonprefix(seqs))
+                    u = st.lcp(*seqs)
                     # both rows plus the shared columns must fit four waves per SIMD (128 VGPRs)
                     if len(seqs[0]) + len(seqs[1]) - u <= 100 and tuple(seqs) not in fused:
                         fused.append(tuple(seqs))
@@ -169,272 +108,239 @@ def collect():
     return fams, templates, fused, members
 
 
-class _Buf(object):
-    def __init__(self):
-        self.parts = []
+def switch(cases, indent="    "):
+    """the cases of a launch switch and its end"""
+    return "".join(indent + "case %s; break;\n" % c for c in cases) + indent + "default: break;\n" + indent + "}\n"
 
-    def write(self, text):
-        self.parts.append(text)
+
+def barcode_families(fams, members):
+    """the chain structs of every family; also the target registry (hash, kernel, case, target), the quad registry
+    (kernel, quad case, pair a, pair b), per family whether it has bit-sliced rows, and those rows
+    (kernel, targets, text of its QBS struct), which go to bs_static_generated.inc"""
+    out, reg, quad_reg, has_bs, bs_structs = [], [], [], [], []
+    for kid, ((up, dn, m), targets) in enumerate(fams.items()):
+        u = len(up)
+        out.append("// kernel %d: %s + barcode + %s (%d columns, %d-column flank, %d targets)\n" % (kid, up, dn, m, u, len(targets)))
+        # targets that are always scanned together (same set of kit groups) may be paired with each other
+        groups = collections.OrderedDict()
+        for t in targets:
+            groups.setdefault(frozenset(members[t]), []).append(t)
+        pairs = []
+        quads = []                                   # (pair index a, pair index b): consecutive pairs of one membership group
+        for grp in groups.values():
+            first = len(pairs)
+            pairs.extend(pair_up(grp, u))
+            if len(targets) >= QUAD_MIN_TARGETS:
+                quads.extend((i, i + 1) for i in range(first, len(pairs) - 1, 2)
+                             if pairs[i][0] != pairs[i][1] and pairs[i + 1][0] != pairs[i + 1][1])
+        cases = []                                   # (case, target): a pair's targets are cases 2 x pair, 2 x pair + 1
+        for pr, (ta, tb, shared) in enumerate(pairs):
+            cases.append((2 * pr, ta))
+            if tb != ta:
+                cases.append((2 * pr + 1, tb))
+            out.append(st.pair_struct("QSP_%d_%d" % (kid, pr), _codes(ta), _codes(tb), shared))
+        reg.extend((fnv1a64(_codes(t)), kid, case, t) for case, t in cases)
+        quad_cases = []
+        for q, (pa, pb) in enumerate(quads):
+            cpa, cpb = [(_codes(a), _codes(b), shared) for a, b, shared in (pairs[pa], pairs[pb])]
+            u0 = st.quad_shared(cpa, cpb)
+            quad_reg.append((kid, q, pa, pb))
+            out.append(st.quad_struct("QSQ_%d_%d" % (kid, q), cpa, cpb, u0))
+            quad_cases.append(("QSQ_%d_%d" % (kid, q), u0, cpa[2] - u0, cpb[2] - u0))
+        out.append(st.group_struct("QSG_%d" % kid, m, quad_cases,
+                                   [("QSP_%d_%d" % (kid, pr), shared) for pr, (_, _, shared) in enumerate(pairs)]))
+        shape = bs_shape(len(up), len(dn), m) if len(targets) >= BS_MIN_TARGETS else None
+        has_bs.append(shape is not None)
+        if shape:
+            rev, pre, own, post = shape
+            bs_structs.append((kid, len(targets), st.bs_row_struct(
+                "QBS_%d" % kid, "%d" % kid, shape, [(case, _codes(t)) for case, t in cases],
+                "%s + barcode + %s: %s, %d shared + %d own + %d trailing columns, %d targets"
+                % (up, dn, "reversed" if rev else "forward", pre, own, post, len(targets)))))
+        out.append("\n")
+    reg.sort()
+    assert len(set(h for h, _, _, _ in reg)) == len(reg), "hash collision between targets"
+    return "".join(out), reg, quad_reg, has_bs, bs_structs
+
+
+def target_registry(fams, reg, quad_reg, has_bs):
+    """the registries static_match reads and the launcher of k_barcode_static"""
+    def ints(values):
+        return ", ".join("%d" % v for v in values)
+    return ("#ifndef QCAT_STATIC_MULTI_TU      // (static_multi.hip takes the column chains above and the merged kernels only)\n"
+            "// (the hash only finds the entry; static_match compares `seq` with the kit's target before binding)\n"
+            "struct StaticTarget { uint64_t hash; int16_t kernel, kase; const char* seq; };\n"
+            "static const StaticTarget g_static_targets[] = {\n"
+            + "".join("    {0x%016XULL, %d, %d, \"%s\"},\n" % r for r in reg)
+            + "};\nstatic const int g_n_static_targets = %d;\n" % len(reg)
+            + "static const int g_static_kernel_M[] = {%s};\n" % ints(m for (_, _, m) in fams)
+            + "// per kernel: upstream / downstream context columns of the family, and whether it has bit-sliced rows (QBS_n)\n"
+            + "static const int g_static_kernel_up[] = {%s};\n" % ints(len(up) for (up, _, _) in fams)
+            + "static const int g_static_kernel_dn[] = {%s};\n" % ints(len(dn) for (_, dn, _) in fams)
+            + "static const int g_static_kernel_bs[] = {%s};\n" % ints(has_bs)
+            + "// quads of a kernel: (kernel, quad case, pair case a, pair case b); a kit group runs them when it scans both pairs\n"
+            "struct StaticQuad { int16_t kernel, quad, pair_a, pair_b; };\n"
+            "static const StaticQuad g_static_quads[] = {\n"
+            + "".join("    {%d, %d, %d, %d},\n" % q for q in quad_reg)
+            + "    {-1, -1, -1, -1}\n};\nstatic const int g_n_static_quads = %d;\n\n" % len(quad_reg)
+            + "static inline void launch_barcode_static(int kernel, dim3 grid, hipStream_t stream, const StaticArgs& a) {\n"
+            "    if (kernel >= QCAT_JIT_BASE) { jit_launch(QCAT_JIT_BARCODE, kernel - QCAT_JIT_BASE, grid, stream, &a); return; }\n"
+            "    switch (kernel) {\n"
+            + switch("%d: hipLaunchKernelGGL(k_barcode_static<QSG_%d>, grid, dim3(PK_WAVES * 64), 0, stream, a)" % (kid, kid)
+                     for kid in range(len(fams)))
+            + "}\n#endif\n\n")
+
+
+def barcode_multi(n_kernels):
+    return ("// every group of a SMALL batch in one launch (packed_host.inc: packed_barcode): blockIdx.x % n = the group.  A kit-auto batch launches\n"
+            "// one kernel per (template, set) group although only the voted kit's groups have jobs, and the runtime's four hardware\n"
+            "// queues serialise them around the two or three that do.  Compiled in a translation unit of its own (static_multi.hip).\n"
+            "#ifdef QCAT_STATIC_MULTI_TU\n"
+            "__global__ void __launch_bounds__(PK_WAVES * 64, 2)\n"
+            "k_barcode_multi(StaticBarcodeMulti m) {\n"
+            "    __shared__ uint8_t qbuf[PK_ROWS * 64];\n"
+            "    const int i = blockIdx.x % (uint32_t)m.n;      // (interleaved: the workgroups of the groups with jobs are resident side by side)\n"
+            "    StaticArgs a = m.common;\n"
+            "    a.gidx = m.gidx[i]; a.chunk_b = m.chunk_b[i];\n"
+            "    switch (m.kernel[i]) {\n"
+            + switch("%d: barcode_static_core<QSG_%d>(a, qbuf)" % (kid, kid) for kid in range(n_kernels))
+            + "}\n"
+            "extern \"C\" void qcat_static_multi_barcode(unsigned grid, void* stream, const void* m) {\n"
+            "    hipLaunchKernelGGL(k_barcode_multi, dim3(grid), dim3(PK_WAVES * 64), 0, static_cast<hipStream_t>(stream), *static_cast<const StaticBarcodeMulti*>(m));\n}\n"
+            "#else\n"
+            "extern \"C\" void qcat_static_multi_barcode(unsigned grid, void* stream, const void* m);\n"
+            "static inline void launch_barcode_multi(dim3 grid, hipStream_t stream, const StaticBarcodeMulti& m) { qcat_static_multi_barcode(grid.x, stream, &m); }\n"
+            "#endif\n\n")
+
+
+def bitslice_parts(bs_structs):
+    """(the launcher of the bit-sliced static-letter kernels, text of bs_static_generated.inc).  They are compiled in
+    translation units of their own (bs_static.hip with QCAT_BS_PART = 0..BS_PARTS-1, in parallel with this one): greedy
+    split by number of targets"""
+    parts = [[] for _ in range(BS_PARTS)]
+    for kid, nt, text in sorted(bs_structs, key=lambda x: -x[1]):
+        min(parts, key=lambda p: sum(n for _, n, _ in p)).append((kid, nt, text))
+    parts = [sorted(part) for part in parts]
+    launcher = ("}  // namespace qk\n#ifndef QCAT_STATIC_MULTI_TU\n"
+                + "".join('extern "C" void qcat_bs_launch_part%d(int kernel, unsigned grid, void* stream, const void* args);   // bs_static.hip\n' % p
+                          for p in range(BS_PARTS))
+                + "#endif\nnamespace qk {\n#ifndef QCAT_STATIC_MULTI_TU\n"
+                "static inline void launch_bs_static(int kernel, dim3 grid, hipStream_t stream, const BsArgs& a) {\n"
+                "    if (kernel >= QCAT_JIT_BASE) { jit_launch(QCAT_JIT_BITSLICE, kernel - QCAT_JIT_BASE, grid, stream, &a); return; }\n"
+                "    switch (kernel) {\n"
+                + "".join("    %s qcat_bs_launch_part%d(kernel, grid.x, stream, &a); break;\n"
+                          % (" ".join("case %d:" % kid for kid, _, _ in part), p) for p, part in enumerate(parts) if part)
+                + "    default: break;\n    }\n}\n#endif\n\n")
+    out = ["// GENERATED by tools/gen_static_kernels.py -- do not edit.\n"
+           "// Bit-sliced barcode kernels with the target letters compiled in (kernels_bitslice.inc), one struct per target\n"
+           "// family; compiled by bs_static.hip in %d parts (QCAT_BS_PART), each in its own namespace.\n\n" % BS_PARTS]
+    for p, part in enumerate(parts):
+        out.append("#if QCAT_BS_PART == %d\nnamespace qk {\n" % p + "".join(text for _, _, text in part) + "}  // namespace qk\n"
+                   + 'extern "C" void qcat_bs_launch_part%d(int kernel, unsigned grid, void* stream, const void* args) {\n'
+                   "    const qk::BsArgs& a = *static_cast<const qk::BsArgs*>(args);\n    switch (kernel) {\n" % p
+                   + switch("%d: hipLaunchKernelGGL(qk::k_bs_barcode<qk::QBS_%d>, dim3(grid), dim3(qk::BS_WAVES * 64), 0, "
+                            "static_cast<hipStream_t>(stream), a)" % (kid, kid) for kid, _, _ in part)
+                   + "}\n#endif\n\n")
+    return launcher, "".join(out)
+
+
+def adapter_templates(templates):
+    """chain struct, registry and launcher of the adapter templates; also the number of registry entries"""
+    out = []
+    for tid, seq in enumerate(templates):
+        out.append("// adapter template %d: %s\n" % (tid, seq) + st.adapter_chain_struct("QAC_%d" % tid, _codes(seq)))
+    areg = sorted((fnv1a64(_codes(seq)), tid, len(seq), seq) for tid, seq in enumerate(templates))
+    assert len(set(h for h, _, _, _ in areg)) == len(areg), "hash collision between templates"
+    out.append("\n#ifndef QCAT_STATIC_MULTI_TU\nstruct StaticTemplate { uint64_t hash; int16_t kernel, len; const char* seq; };\n"
+               "static const StaticTemplate g_static_templates[] = {\n"
+               + "".join("    {0x%016XULL, %d, %d, \"%s\"},\n" % r for r in areg)
+               + "};\nstatic const int g_n_static_templates = %d;\n\n" % len(areg)
+               + "static inline void launch_adapter_static(int kernel, dim3 grid, hipStream_t stream, const StaticAdapterArgs& a) {\n"
+               "    if (kernel >= QCAT_JIT_BASE) { jit_launch(QCAT_JIT_ADAPTER, kernel - QCAT_JIT_BASE, grid, stream, &a); return; }\n"
+               "    switch (kernel) {\n"
+               + switch("%d: hipLaunchKernelGGL((k_adapter_static<%d, QAC_%d>), grid, dim3(PK_WAVES * 64), 0, stream, a)" % (tid, len(seq), tid)
+                        for tid, seq in enumerate(templates))
+               + "}\n#endif\n\n")
+    return "".join(out)
+
+
+def fused_args(fused):
+    """per two-template kit the template arguments of its fused kernel: shared columns, both lengths, chain struct"""
+    return ["%d, %d, %d, QAF_%d" % (st.lcp(sa, sb), len(sa), len(sb), fid) for fid, (sa, sb) in enumerate(fused)]
+
+
+def fused_kits(templates, fused):
+    """two-template kits: one fused pass over both templates"""
+    out = []
+    for fid, (sa, sb) in enumerate(fused):
+        u = st.lcp(sa, sb)
+        out.append("// fused adapter kernel %d: %d shared columns of\n//   %s\n//   %s\n" % (fid, u, sa, sb)
+                   + "struct QAF_%d {\n" % fid
+                   + st.chain_fn("pre", _codes(sa[:u]), 5) + st.chain_fn("ta", _codes(sa[u:]), 5) + st.chain_fn("tb", _codes(sb[u:]), 5) + "};\n")
+    out.append("\n#ifndef QCAT_STATIC_MULTI_TU\n// (tpl_a / tpl_b: the static adapter kernels of the two templates, which static_match has verified)\n"
+               "struct StaticFused { int16_t tpl_a, tpl_b, kernel; };\n"
+               "static const StaticFused g_static_fused[] = {\n"
+               + "".join("    {%d, %d, %d},\n" % (templates.index(sa), templates.index(sb), fid) for fid, (sa, sb) in enumerate(fused))
+               + "};\nstatic const int g_n_static_fused = %d;\n\n" % len(fused)
+               + "static inline void launch_adapter_fused(int kernel, dim3 grid, hipStream_t stream, const StaticAdapterArgs& a) {\n"
+               "    switch (kernel) {\n"
+               + switch("%d: hipLaunchKernelGGL((k_adapter_fused2<%s>), grid, dim3(PK_WAVES * 64), 0, stream, a)" % (fid, args)
+                        for fid, args in enumerate(fused_args(fused)))
+               + "}\n#endif\n\n")
+    return "".join(out)
+
+
+def adapter_multi(templates, fused):
+    return ("// every static-letter adapter chain of a SMALL batch in one launch (packed_host.inc: packed_adapter): blockIdx.y = the unit --\n"
+            "// a template or a fused pair.  The units of such a batch are latency chains (one wave per SIMD, 50-110 us each for the\n"
+            "// 4000 reads of the reference driver's call), and launches of their own are serialised by the runtime's four hardware queues.\n"
+            "#ifdef QCAT_STATIC_MULTI_TU\n"
+            "__global__ void __launch_bounds__(PK_WAVES * 64, 2)\n"
+            "k_adapter_multi(StaticAdapterMulti m) {\n"
+            "    __shared__ uint8_t qbuf[PK_ROWS * 64];\n"
+            "    __shared__ uint16_t slow_tbl[5 * 16];\n"
+            "    const int i = blockIdx.y;\n"
+            "    StaticAdapterArgs a = m.common;\n"
+            "    a.bests = m.bests[i]; a.bests2 = m.bests2[i]; a.tpl = m.tpl[i]; a.tpl2 = m.tpl2[i];\n"
+            "    const int kernel = m.kernel[i];\n"
+            "    if (m.fused[i]) {\n"
+            "        switch (kernel) {\n"
+            + switch(("%d: adapter_fused2_core<%s>(a, qbuf, slow_tbl)" % (fid, args) for fid, args in enumerate(fused_args(fused))), "        ")
+            + "    } else {\n        switch (kernel) {\n"
+            + switch(("%d: adapter_static_core<%d, QAC_%d>(a, qbuf, slow_tbl)" % (tid, len(seq), tid) for tid, seq in enumerate(templates)), "        ")
+            + "    }\n}\n"
+            "extern \"C\" void qcat_static_multi_adapter(unsigned grid_x, unsigned grid_y, void* stream, const void* m) {\n"
+            "    hipLaunchKernelGGL(k_adapter_multi, dim3(grid_x, grid_y), dim3(PK_WAVES * 64), 0, static_cast<hipStream_t>(stream), *static_cast<const StaticAdapterMulti*>(m));\n}\n"
+            "#else\n"
+            "extern \"C\" void qcat_static_multi_adapter(unsigned grid_x, unsigned grid_y, void* stream, const void* m);\n"
+            "static inline void launch_adapter_multi(dim3 grid, hipStream_t stream, const StaticAdapterMulti& m) { qcat_static_multi_adapter(grid.x, grid.y, stream, &m); }\n"
+            "#endif\n\n")
+
+
+def middle_launcher(templates):
+    return ("// the same column chains over the read interior (--detect-middle, kernels_middle.inc)\n"
+            "#ifdef QCAT_HAVE_MIDDLE_KERNELS\n"
+            "static inline void launch_adapter_middle(int kernel, dim3 grid, hipStream_t stream, const MiddleAdapterArgs& a) {\n"
+            "    if (kernel >= QCAT_JIT_BASE) { jit_launch(QCAT_JIT_MIDDLE, kernel - QCAT_JIT_BASE, grid, stream, &a); return; }\n"
+            "    switch (kernel) {\n"
+            + switch("%d: hipLaunchKernelGGL((k_adapter_middle<%d, QAC_%d>), grid, dim3(PK_WAVES * 64), 0, stream, a)" % (tid, len(seq), tid)
+                     for tid, seq in enumerate(templates))
+            + "}\n#endif\n\n")
 
 
 def render():
-    """text of static_generated.inc plus (n kernels, n targets, n templates)"""
+    """text of static_generated.inc, (n kernels, n targets, n templates), text of bs_static_generated.inc"""
     fams, templates, fused, members = collect()
-    reg = []
-    bs_fams = []                                     # (kernel, upstream columns, downstream columns, has bit-sliced rows)
-    bs_structs = []                                  # (kernel, targets, text of its QBS struct) -> bs_static_generated.inc
-    quad_reg = []                                    # (kernel, quad case, pair a, pair b)
-    fh = _Buf()
-    if True:
-        fh.write("// GENERATED by tools/gen_static_kernels.py -- do not edit.\n")
-        fh.write("// %d kernels, %d targets (built-in kits, barcode_context_length = %d).\n\n"
-                 % (len(fams), sum(len(v) for v in fams.values()), qconfig.qcatConfig().barcode_context_length))
-        fh.write("namespace qk {\n\n")
-        for kid, ((up, dn, m), targets) in enumerate(fams.items()):
-            u = len(up)
-            fh.write("// kernel %d: %s + barcode + %s (%d columns, %d-column flank, %d targets)\n" % (kid, up, dn, m, u, len(targets)))
-            # targets that are always scanned together (same set of kit groups) may be paired with each other
-            groups = collections.OrderedDict()
-            for t in targets:
-                groups.setdefault(frozenset(members[t]), []).append(t)
-            pairs = []
-            quads = []                                   # (pair index a, pair index b): consecutive pairs of one membership group
-            for grp in groups.values():
-                first = len(pairs)
-                pairs.extend(pair_up(grp, u))
-                if len(targets) >= QUAD_MIN_TARGETS:
-                    quads.extend((i, i + 1) for i in range(first, len(pairs) - 1, 2)
-                                 if pairs[i][0] != pairs[i][1] and pairs[i + 1][0] != pairs[i + 1][1])
-            npairs = len(pairs)
-            for pr, (ta, tb, up_) in enumerate(pairs):
-                reg.append((fnv1a64([CODE[c] for c in ta]), kid, 2 * pr, ta))
-                if tb != ta:
-                    reg.append((fnv1a64([CODE[c] for c in tb]), kid, 2 * pr + 1, tb))
-                fh.write("struct QSP_%d_%d {      // %d shared columns\n" % (kid, pr, up_))
-                fh.write("    static __device__ __forceinline__ void pre(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[4]) { %s }\n"
-                         % (up_ + 1, chain(ta[:up_], CODE) if up_ else ""))
-                for name, t in (("ta", ta), ("tb", tb)):
-                    fh.write("    static __device__ __forceinline__ void %s(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[4]) { %s }\n"
-                             % (name, m - up_ + 1, chain(t[up_:], CODE)))
-                fh.write("};\n")
-            # quads: two pairs in ONE row pass -- the columns all four targets share (at least the flank) and the
-            # per-row work (selector, score registers, boundary) are paid once per four targets (static_barcode_rows4)
-            for q, (pa, pb) in enumerate(quads):
-                (a1, a2, ua), (b1, b2, ub) = pairs[pa], pairs[pb]
-                u0 = min(len(os.path.commonprefix([a1, a2, b1, b2])), ua, ub)
-                quad_reg.append((kid, q, pa, pb))
-                fh.write("struct QSQ_%d_%d {      // %d columns shared by all four, +%d / +%d inside the pairs\n" % (kid, q, u0, ua - u0, ub - u0))
-                fh.write("    static __device__ __forceinline__ void pre0(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[4]) { %s }\n"
-                         % (u0 + 1, chain(a1[:u0], CODE) if u0 else ""))
-                for name, t, lo, hi in (("prea", a1, u0, ua), ("ta", a1, ua, m), ("tb", a2, ua, m),
-                                        ("preb", b1, u0, ub), ("tc", b1, ub, m), ("td", b2, ub, m)):
-                    fh.write("    static __device__ __forceinline__ void %s(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[4]) { %s }\n"
-                             % (name, hi - lo + 1, chain(t[lo:hi], CODE) if hi > lo else ""))
-                fh.write("};\n")
-            nq = len(quads)
-            fh.write("struct QSG_%d {\n    static constexpr int M = %d;\n    static constexpr int HAS_QUADS = %d;\n" % (kid, m, 1 if nq else 0))
-            fh.write("    static __device__ __forceinline__ void run4(int quad, const uint8_t* qbuf, int lane, int Lmax, h2 gL2, "
-                     "u32 special, const u32 (&ltr)[4], h2 rowoff, h2 coloff, u32& ra, u32& rb, u32& rc, u32& rd) {\n"
-                     "        ra = 0; rb = 0; rc = 0; rd = 0;\n        switch (quad) {\n")
-            for q, (pa, pb) in enumerate(quads):
-                (a1, a2, ua), (b1, b2, ub) = pairs[pa], pairs[pb]
-                u0 = min(len(os.path.commonprefix([a1, a2, b1, b2])), ua, ub)
-                fh.write("        case %d: static_barcode_rows4<M, %d, %d, %d, QSQ_%d_%d>(qbuf, lane, Lmax, gL2, special, ltr, rowoff, coloff, ra, rb, rc, rd); break;\n"
-                         % (q, u0, ua - u0, ub - u0, kid, q))
-            fh.write("        default: break;\n        }\n    }\n")
-            fh.write("    static __device__ __forceinline__ void run(int pair, const uint8_t* qbuf, int lane, int Lmax, h2 gL2, "
-                     "u32 special, const u32 (&ltr)[4], h2 rowoff, h2 coloff, u32& ra, u32& rb) {\n        ra = 0; rb = 0;\n        switch (pair) {\n")
-            for pr, (ta, tb, up_) in enumerate(pairs):
-                fh.write("        case %d: static_barcode_rows2<M, %d, QSP_%d_%d>(qbuf, lane, Lmax, gL2, special, ltr, rowoff, coloff, ra, rb); break;\n"
-                         % (pr, up_, kid, pr))
-            fh.write("        default: break;\n        }\n    }\n};\n")
-            shape = bs_shape(len(up), len(dn), m) if len(targets) >= BS_MIN_TARGETS else None
-            bs_fams.append((kid, len(up), len(dn), shape is not None))
-            if shape:
-                rev, pre, own, post = shape
-                bh = _Buf()
-                bh.write("struct QBS_%d {      // %s + barcode + %s: %s, %d shared + %d own + %d trailing columns, %d targets\n"
-                         % (kid, up, dn, "reversed" if rev else "forward", pre, own, post, len(targets)))
-                s1, s0 = bs_shared_words(targets[0], rev, pre, CODE)
-                t1, t0 = bs_trailing_words(targets[0], rev, post, CODE)
-                bh.write("    static constexpr int C = %d, KERNEL = %d, PRE = %d, POST = %d;\n"
-                         "    static constexpr unsigned S1 = 0x%Xu, S0 = 0x%Xu;      // letters of the shared columns\n"
-                         "    static constexpr unsigned T1 = 0x%Xu, T0 = 0x%Xu;      // letters of the trailing columns, last column first\n"
-                         % (own, kid, pre, post, s1, s0, t1, t0))
-                bh.write("    static __device__ __forceinline__ void rows(int kase, const BsRowArgs& ra, "
-                         "u32 (&h1)[C], u32 (&h0)[C], u32 (&f)[BS_ND]) {\n        switch (kase) {\n")
-                for pr, (ta, tb, up_) in enumerate(pairs):
-                    for half, t in ((0, ta), (1, tb)):
-                        if half == 1 and tb == ta:
-                            continue
-                        w1, w0 = bs_words(t, rev, pre, CODE, own)
-                        bh.write("        case %d: bs_rows_static<C, PRE != 0, 0x%XULL, 0x%XULL>(ra, h1, h0, f); break;\n"
-                                 % (2 * pr + half, w1, w0))
-                bh.write("        default: break;\n        }\n    }\n};\n")
-                bs_structs.append((kid, len(targets), "".join(bh.parts)))
-            fh.write("\n")
-        reg.sort()
-        assert len(set(h for h, _, _, _ in reg)) == len(reg), "hash collision between targets"
-        fh.write("#ifndef QCAT_STATIC_MULTI_TU      // (static_multi.hip takes the column chains above and the merged kernels only)\n")
-        fh.write("// (the hash only finds the entry; static_match compares `seq` with the kit's target before binding)\n")
-        fh.write("struct StaticTarget { uint64_t hash; int16_t kernel, kase; const char* seq; };\n")
-        fh.write("static const StaticTarget g_static_targets[] = {\n")
-        for h, kid, case, seq in reg:
-            fh.write("    {0x%016XULL, %d, %d, \"%s\"},\n" % (h, kid, case, seq))
-        fh.write("};\nstatic const int g_n_static_targets = %d;\n" % len(reg))
-        fh.write("static const int g_static_kernel_M[] = {%s};\n" % ", ".join(str(m) for (_, _, m) in fams))
-        fh.write("// per kernel: upstream / downstream context columns of the family, and whether it has bit-sliced rows (QBS_n)\n")
-        fh.write("static const int g_static_kernel_up[] = {%s};\n" % ", ".join(str(u) for (_, u, _, _) in bs_fams))
-        fh.write("static const int g_static_kernel_dn[] = {%s};\n" % ", ".join(str(d) for (_, _, d, _) in bs_fams))
-        fh.write("static const int g_static_kernel_bs[] = {%s};\n" % ", ".join("1" if b else "0" for (_, _, _, b) in bs_fams))
-        fh.write("// quads of a kernel: (kernel, quad case, pair case a, pair case b); a kit group runs them when it scans both pairs\n")
-        fh.write("struct StaticQuad { int16_t kernel, quad, pair_a, pair_b; };\n")
-        fh.write("static const StaticQuad g_static_quads[] = {\n")
-        for kid, q, pa, pb in quad_reg:
-            fh.write("    {%d, %d, %d, %d},\n" % (kid, q, pa, pb))
-        fh.write("    {-1, -1, -1, -1}\n};\nstatic const int g_n_static_quads = %d;\n\n" % len(quad_reg))
-        fh.write("static inline void launch_barcode_static(int kernel, dim3 grid, hipStream_t stream, const StaticArgs& a) {\n"
-                 "    if (kernel >= QCAT_JIT_BASE) { jit_launch(QCAT_JIT_BARCODE, kernel - QCAT_JIT_BASE, grid, stream, &a); return; }\n"
-                 "    switch (kernel) {\n")
-        for kid in range(len(fams)):
-            fh.write("    case %d: hipLaunchKernelGGL(k_barcode_static<QSG_%d>, grid, dim3(PK_WAVES * 64), 0, stream, a); break;\n" % (kid, kid))
-        fh.write("    default: break;\n    }\n}\n#endif\n\n")
-        fh.write("// every group of a SMALL batch in one launch (packed_host.inc: packed_barcode): blockIdx.x % n = the group.  A kit-auto batch launches\n"
-                 "// one kernel per (template, set) group although only the voted kit's groups have jobs, and the runtime's four hardware\n"
-                 "// queues serialise them around the two or three that do.  Compiled in a translation unit of its own (static_multi.hip).\n"
-                 "#ifdef QCAT_STATIC_MULTI_TU\n"
-                 "__global__ void __launch_bounds__(PK_WAVES * 64, 2)\n"
-                 "k_barcode_multi(StaticBarcodeMulti m) {\n"
-                 "    __shared__ uint8_t qbuf[PK_ROWS * 64];\n"
-                 "    const int i = blockIdx.x % (uint32_t)m.n;      // (interleaved: the workgroups of the groups with jobs are resident side by side)\n"
-                 "    StaticArgs a = m.common;\n"
-                 "    a.gidx = m.gidx[i]; a.chunk_b = m.chunk_b[i];\n"
-                 "    switch (m.kernel[i]) {\n")
-        for kid in range(len(fams)):
-            fh.write("    case %d: barcode_static_core<QSG_%d>(a, qbuf); break;\n" % (kid, kid))
-        fh.write("    default: break;\n    }\n}\n"
-                 "extern \"C\" void qcat_static_multi_barcode(unsigned grid, void* stream, const void* m) {\n"
-                 "    hipLaunchKernelGGL(k_barcode_multi, dim3(grid), dim3(PK_WAVES * 64), 0, static_cast<hipStream_t>(stream), *static_cast<const StaticBarcodeMulti*>(m));\n}\n"
-                 "#else\n"
-                 "extern \"C\" void qcat_static_multi_barcode(unsigned grid, void* stream, const void* m);\n"
-                 "static inline void launch_barcode_multi(dim3 grid, hipStream_t stream, const StaticBarcodeMulti& m) { qcat_static_multi_barcode(grid.x, stream, &m); }\n"
-                 "#endif\n\n")
-        # the bit-sliced static-letter kernels are compiled in translation units of their own (bs_static.hip with
-        # QCAT_BS_PART = 0..BS_PARTS-1, in parallel with this one): greedy split by number of targets
-        parts = [[] for _ in range(BS_PARTS)]
-        for kid, nt, text in sorted(bs_structs, key=lambda x: -x[1]):
-            min(parts, key=lambda p: sum(n for _, n, _ in p)).append((kid, nt, text))
-        fh.write("}  // namespace qk\n#ifndef QCAT_STATIC_MULTI_TU\n")
-        for p in range(BS_PARTS):
-            fh.write('extern "C" void qcat_bs_launch_part%d(int kernel, unsigned grid, void* stream, const void* args);   // bs_static.hip\n' % p)
-        fh.write("#endif\nnamespace qk {\n#ifndef QCAT_STATIC_MULTI_TU\n")
-        fh.write("static inline void launch_bs_static(int kernel, dim3 grid, hipStream_t stream, const BsArgs& a) {\n"
-                 "    if (kernel >= QCAT_JIT_BASE) { jit_launch(QCAT_JIT_BITSLICE, kernel - QCAT_JIT_BASE, grid, stream, &a); return; }\n"
-                 "    switch (kernel) {\n")
-        for p, part in enumerate(parts):
-            if part:
-                fh.write("    %s qcat_bs_launch_part%d(kernel, grid.x, stream, &a); break;\n"
-                         % (" ".join("case %d:" % kid for kid, _, _ in sorted(part)), p))
-        fh.write("    default: break;\n    }\n}\n#endif\n\n")
-        bparts = ["// GENERATED by tools/gen_static_kernels.py -- do not edit.\n"
-                  "// Bit-sliced barcode kernels with the target letters compiled in (kernels_bitslice.inc), one struct per target\n"
-                  "// family; compiled by bs_static.hip in %d parts (QCAT_BS_PART), each in its own namespace.\n\n" % BS_PARTS]
-        for p, part in enumerate(parts):
-            bparts.append("#if QCAT_BS_PART == %d\nnamespace qk {\n" % p)
-            for kid, _, text in sorted(part):
-                bparts.append(text)
-            bparts.append("}  // namespace qk\n")
-            bparts.append('extern "C" void qcat_bs_launch_part%d(int kernel, unsigned grid, void* stream, const void* args) {\n'
-                          "    const qk::BsArgs& a = *static_cast<const qk::BsArgs*>(args);\n    switch (kernel) {\n" % p)
-            for kid, _, _ in sorted(part):
-                bparts.append("    case %d: hipLaunchKernelGGL(qk::k_bs_barcode<qk::QBS_%d>, dim3(grid), dim3(qk::BS_WAVES * 64), 0, "
-                              "static_cast<hipStream_t>(stream), a); break;\n" % (kid, kid))
-            bparts.append("    default: break;\n    }\n}\n#endif\n\n")
-        bs_text = "".join(bparts)
-        # ---- adapter templates ------------------------------------------------------------------
-        areg = []
-        for tid, seq in enumerate(templates):
-            cols = chain(seq, ACODE)
-            fh.write("// adapter template %d: %s\n" % (tid, seq))
-            fh.write("struct QAC_%d { static __device__ __forceinline__ void run(h2 (&h)[%d], h2& carry, h2& left, "
-                     "const h2 (&E)[5]) { %s } };\n" % (tid, len(seq) + 1, cols))
-            areg.append((fnv1a64([ACODE[c] for c in seq]), tid, len(seq), seq))
-        areg.sort()
-        assert len(set(h for h, _, _, _ in areg)) == len(areg), "hash collision between templates"
-        fh.write("\n#ifndef QCAT_STATIC_MULTI_TU\nstruct StaticTemplate { uint64_t hash; int16_t kernel, len; const char* seq; };\n")
-        fh.write("static const StaticTemplate g_static_templates[] = {\n")
-        for h, tid, m, seq in areg:
-            fh.write("    {0x%016XULL, %d, %d, \"%s\"},\n" % (h, tid, m, seq))
-        fh.write("};\nstatic const int g_n_static_templates = %d;\n\n" % len(areg))
-        fh.write("static inline void launch_adapter_static(int kernel, dim3 grid, hipStream_t stream, const StaticAdapterArgs& a) {\n"
-                 "    if (kernel >= QCAT_JIT_BASE) { jit_launch(QCAT_JIT_ADAPTER, kernel - QCAT_JIT_BASE, grid, stream, &a); return; }\n"
-                 "    switch (kernel) {\n")
-        for tid, seq in enumerate(templates):
-            fh.write("    case %d: hipLaunchKernelGGL((k_adapter_static<%d, QAC_%d>), grid, dim3(PK_WAVES * 64), 0, stream, a); break;\n"
-                     % (tid, len(seq), tid))
-        fh.write("    default: break;\n    }\n}\n#endif\n\n")
-        # ---- two-template kits: one fused pass ----------------------------------------------------
-        for fid, (sa, sb) in enumerate(fused):
-            u = len(os.path.commonprefix([sa, sb]))
-            fh.write("// fused adapter kernel %d: %d shared columns of\n//   %s\n//   %s\n" % (fid, u, sa, sb))
-            fh.write("struct QAF_%d {\n" % fid)
-            fh.write("    static __device__ __forceinline__ void pre(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[5]) { %s }\n"
-                     % (u + 1, chain(sa[:u], ACODE) if u else ""))
-            for name, q in (("ta", sa), ("tb", sb)):
-                fh.write("    static __device__ __forceinline__ void %s(h2 (&h)[%d], h2& carry, h2& left, const h2 (&E)[5]) { %s }\n"
-                         % (name, len(q) - u + 1, chain(q[u:], ACODE)))
-            fh.write("};\n")
-        fh.write("\n#ifndef QCAT_STATIC_MULTI_TU\n// (tpl_a / tpl_b: the static adapter kernels of the two templates, which static_match has verified)\n")
-        fh.write("struct StaticFused { int16_t tpl_a, tpl_b, kernel; };\n")
-        fh.write("static const StaticFused g_static_fused[] = {\n")
-        for fid, (sa, sb) in enumerate(fused):
-            fh.write("    {%d, %d, %d},\n" % (templates.index(sa), templates.index(sb), fid))
-        fh.write("};\nstatic const int g_n_static_fused = %d;\n\n" % len(fused))
-        fh.write("static inline void launch_adapter_fused(int kernel, dim3 grid, hipStream_t stream, const StaticAdapterArgs& a) {\n"
-                 "    switch (kernel) {\n")
-        for fid, (sa, sb) in enumerate(fused):
-            u = len(os.path.commonprefix([sa, sb]))
-            fh.write("    case %d: hipLaunchKernelGGL((k_adapter_fused2<%d, %d, %d, QAF_%d>), grid, dim3(PK_WAVES * 64), 0, stream, a); break;\n"
-                     % (fid, u, len(sa), len(sb), fid))
-        fh.write("    default: break;\n    }\n}\n#endif\n\n")
-        # ---- every chain of a small batch in one launch ------------------------------------------
-        fh.write("// every static-letter adapter chain of a SMALL batch in one launch (packed_host.inc: packed_adapter): blockIdx.y = the unit --\n"
-                 "// a template or a fused pair.  The units of such a batch are latency chains (one wave per SIMD, 50-110 us each for the\n"
-                 "// 4000 reads of the reference driver's call), and launches of their own are serialised by the runtime's four hardware queues.\n"
-                 "#ifdef QCAT_STATIC_MULTI_TU\n"
-                 "__global__ void __launch_bounds__(PK_WAVES * 64, 2)\n"
-                 "k_adapter_multi(StaticAdapterMulti m) {\n"
-                 "    __shared__ uint8_t qbuf[PK_ROWS * 64];\n"
-                 "    __shared__ uint16_t slow_tbl[5 * 16];\n"
-                 "    const int i = blockIdx.y;\n"
-                 "    StaticAdapterArgs a = m.common;\n"
-                 "    a.bests = m.bests[i]; a.bests2 = m.bests2[i]; a.tpl = m.tpl[i]; a.tpl2 = m.tpl2[i];\n"
-                 "    const int kernel = m.kernel[i];\n"
-                 "    if (m.fused[i]) {\n"
-                 "        switch (kernel) {\n")
-        for fid, (sa, sb) in enumerate(fused):
-            u = len(os.path.commonprefix([sa, sb]))
-            fh.write("        case %d: adapter_fused2_core<%d, %d, %d, QAF_%d>(a, qbuf, slow_tbl); break;\n" % (fid, u, len(sa), len(sb), fid))
-        fh.write("        default: break;\n        }\n    } else {\n        switch (kernel) {\n")
-        for tid, seq in enumerate(templates):
-            fh.write("        case %d: adapter_static_core<%d, QAC_%d>(a, qbuf, slow_tbl); break;\n" % (tid, len(seq), tid))
-        fh.write("        default: break;\n        }\n    }\n}\n"
-                 "extern \"C\" void qcat_static_multi_adapter(unsigned grid_x, unsigned grid_y, void* stream, const void* m) {\n"
-                 "    hipLaunchKernelGGL(k_adapter_multi, dim3(grid_x, grid_y), dim3(PK_WAVES * 64), 0, static_cast<hipStream_t>(stream), *static_cast<const StaticAdapterMulti*>(m));\n}\n"
-                 "#else\n"
-                 "extern \"C\" void qcat_static_multi_adapter(unsigned grid_x, unsigned grid_y, void* stream, const void* m);\n"
-                 "static inline void launch_adapter_multi(dim3 grid, hipStream_t stream, const StaticAdapterMulti& m) { qcat_static_multi_adapter(grid.x, grid.y, stream, &m); }\n"
-                 "#endif\n\n")
-        fh.write("// the same column chains over the read interior (--detect-middle, kernels_middle.inc)\n")
-        fh.write("#ifdef QCAT_HAVE_MIDDLE_KERNELS\n")
-        fh.write("static inline void launch_adapter_middle(int kernel, dim3 grid, hipStream_t stream, const MiddleAdapterArgs& a) {\n"
-                 "    if (kernel >= QCAT_JIT_BASE) { jit_launch(QCAT_JIT_MIDDLE, kernel - QCAT_JIT_BASE, grid, stream, &a); return; }\n"
-                 "    switch (kernel) {\n")
-        for tid, seq in enumerate(templates):
-            fh.write("    case %d: hipLaunchKernelGGL((k_adapter_middle<%d, QAC_%d>), grid, dim3(PK_WAVES * 64), 0, stream, a); break;\n"
-                     % (tid, len(seq), tid))
-        fh.write("    default: break;\n    }\n}\n#endif\n\n}  // namespace qk\n")
-    return "".join(fh.parts), len(fams), len(reg), len(templates), bs_text
+    families, reg, quad_reg, has_bs, bs_structs = barcode_families(fams, members)
+    bs_launcher, bs_text = bitslice_parts(bs_structs)
+    text = ("// GENERATED by tools/gen_static_kernels.py -- do not edit.\n"
+            "// %d kernels, %d targets (built-in kits, barcode_context_length = %d).\n\n"
+            % (len(fams), sum(len(v) for v in fams.values()), qconfig.qcatConfig().barcode_context_length)
+            + "namespace qk {\n\n"
+            + families + target_registry(fams, reg, quad_reg, has_bs) + barcode_multi(len(fams)) + bs_launcher
+            + adapter_templates(templates) + fused_kits(templates, fused) + adapter_multi(templates, fused)
+            + middle_launcher(templates) + "}  // namespace qk\n")
+    return text, len(fams), len(reg), len(templates), bs_text
 
 
 def main():
