@@ -30,9 +30,9 @@ __device__ __forceinline__ uint32_t dev_code_of(uint32_t c) {
 // with QCAT_ENDS_5P only side 0 exists.  Codes beyond the window length are PAD.  In code space
 // the complement is `code ^ 1` for A,T,G,C and the identity for everything else (IUPAC letters
 // map to "other" before and after complementing).
-// One thread produces 16 consecutive codes (one 16-byte store); a window is 10 threads.  The 16
-// source bytes are fetched as five aligned dwords and funnel-shifted into place (the batch buffer
-// has slack on both sides), and converted four at a time:  idx = (c & 0xDF) >> 1 & 7 separates
+// One thread produces 32 consecutive codes; a window is 5 threads.  The 32 source bytes are fetched
+// as nine aligned dwords and funnel-shifted into place (the batch buffer has slack on both
+// sides), and converted four at a time:  idx = (c & 0xDF) >> 1 & 7 separates
 // A, C, G, T, N, X; one v_perm_b32 maps idx to the code, a second one to the letter idx stands
 // for, and a byte that is not that letter becomes "other".
 // ---------------------------------------------------------------------------------------------
@@ -43,8 +43,8 @@ __device__ __forceinline__ uint32_t dev_codes_of4(uint32_t w) {
     const uint32_t expect = __builtin_amdgcn_perm(0x4EFFFF58u, 0x47544341u, idx); // 'A' 'C' 'T' 'G' | 'X' - - 'N'
     const uint32_t diff = u ^ expect;
     const uint32_t nz = (((diff & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | diff) & 0x80808080u;   // bit 7 of every non-zero byte
-    const uint32_t m = (nz >> 7) * 0xFFu;
-    return (code & ~m) | (0x06060606u & m);
+    const uint32_t m = nz - (nz >> 7);                   // 0x7F in every flagged byte, all a code's bits (0x80 - 0x01 borrows nothing; a 32-bit multiply is quarter rate)
+    return __builtin_amdgcn_bitop3_b32(code, 0x06060606u, m, 0xD8u);       // m ? 6 : code
 }
 
 // 16 bytes starting at the (unaligned) address p, as four dwords in address order
@@ -113,43 +113,97 @@ __device__ __forceinline__ void dev_window_codes16(const uint8_t* p0, const uint
     }
 }
 
-__global__ void __launch_bounds__(256)
+// 32 bytes starting at the (unaligned) address p, as eight dwords in address order
+__device__ __forceinline__ void dev_load32_unaligned(const uint8_t* p, uint32_t (&w)[8]) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+    const uint32_t sh = (uint32_t)(a & 3);
+    uint32_t r[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r[i] = q[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = __builtin_amdgcn_alignbyte(r[i + 1], r[i], sh);
+}
+
+// 32 codes per thread: 36 bytes in flight per lane, and the index and length arithmetic once per 32 codes.  A workgroup is
+// PACK_WINDOWS windows, so window and part come from the thread index by one multiply, and ENDS is a template argument (the
+// first form, one thread per 16 codes, divided a 64-bit global index by 10 and by `ends`).  The two sides share one
+// instruction stream: the side picks the address, the byte order (v_perm selector) and the complement mask, where a branch
+// made every wave -- windows of both sides in each -- walk both bodies.  That form was bound by the VALU, not by its bytes
+// (DESIGN.md 3.1: 308 VALU instructions per wave, 1.57 of its 1.59 ms per 10 M reads; now 1.04 ms).
+constexpr uint32_t PACK_CODES = 32;                                      // codes per thread
+constexpr uint32_t PACK_PARTS = WIN_STRIDE / PACK_CODES;                 // 5
+constexpr uint32_t PACK_WINDOWS = 64;
+constexpr uint32_t PACK_THREADS = PACK_WINDOWS * PACK_PARTS;
+
+template <int ENDS>
+__global__ void __launch_bounds__(PACK_THREADS)
 k_pack_windows(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offsets,
-               uint32_t n_reads, int ends, int max_align,
+               uint32_t n_reads, int max_align,
                uint8_t* __restrict__ win, int32_t* __restrict__ wlen, uint8_t* __restrict__ wspec,
                uint32_t* __restrict__ win2 /* two bits per code beside the bytes (WIN2_WORDS dwords per window; meaningful for
                                               windows of plain A, C, G, T): what the bit-sliced kernels read; or null */,
                int lazy_bytes = 0 /* 1: no byte windows here -- k_expand_special writes those of the flagged ends, every reader
                                      expands the others from win2 (dev_window16): 3.3 GB less to write per 10 M reads */) {
-    const uint32_t chunks = WIN_STRIDE / 16;
-    uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t e = gid / chunks;
-    uint32_t chunk = (uint32_t)(gid % chunks);
-    if (e >= (uint64_t)n_reads * ends) return;
-    uint64_t r = e / ends;
-    int side = (int)(e % ends);
+    static_assert(ENDS == 1 || ENDS == 2, "one or two windows per read");
+    static_assert(PACK_PARTS == 5 && PACK_PARTS * PACK_CODES == WIN_STRIDE && PACK_THREADS < 1000, "threadIdx.x / 5 below is (x * 205) >> 10");
+    const uint32_t wl = (threadIdx.x * 205u) >> 10;
+    const uint32_t part = threadIdx.x - wl * PACK_PARTS;
+    const uint64_t e = (uint64_t)blockIdx.x * PACK_WINDOWS + wl;
+    if (e >= (uint64_t)n_reads * ENDS) return;
+    const uint64_t r = ENDS == 2 ? e >> 1 : e;
+    const uint32_t side = ENDS == 2 ? (uint32_t)e & 1u : 0u;
     uint64_t beg = offsets[r], end = offsets[r + 1];
     uint64_t len = end - beg;
     int L = len < (uint64_t)max_align ? (int)len : max_align;
-    if (chunk == 0) wlen[e] = L;
-    uint32_t out[4];
-    dev_window_codes16(bases + beg, bases + end, side, (int)chunk * 16, L, out);
-    if (!lazy_bytes) *reinterpret_cast<uint4*>(win + e * WIN_STRIDE + chunk * 16) = make_uint4(out[0], out[1], out[2], out[3]);
-    if (win2) {                  // code i of the chunk in bits 2 i, 2 i + 1 of its dword
-        uint32_t p = 0;
+    if (part == 0) wlen[e] = L;
+    const int i0 = (int)(part * PACK_CODES);
+    constexpr int NW = PACK_CODES / 4;
+    uint32_t out[NW];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            uint32_t t = out[q] & 0x03030303u;
-            t = (t | (t >> 6)) & 0x000F000Fu;
-            t = (t | (t >> 12)) & 0xFFu;
-            p |= t << (8 * q);
+    for (int q = 0; q < NW; ++q) out[q] = 0x07070707u;
+    if (i0 < L) {
+        // dev_window_codes16 with the side as data: side 1 reads the 32 bytes below end - i0, reverses them and complements the codes
+        uint32_t w[NW];
+        dev_load32_unaligned(bases + (side ? end - (uint64_t)i0 - PACK_CODES : beg + (uint64_t)i0), w);
+        const uint32_t rev = 0u - side;                                  // all ones on side 1
+        const uint32_t order = side ? 0x00010203u : 0x03020100u, comp = rev & 0x01010101u;
+        const int n8 = 8 * (L - i0);                                     // bits of these codes inside the window
+#pragma unroll
+        for (int q = 0; q < NW; ++q) {
+            const uint32_t x = __builtin_amdgcn_bitop3_b32(w[q], w[NW - 1 - q], rev, 0xD8u);   // rev ? w[NW - 1 - q] : w[q]
+            uint32_t c = dev_codes_of4(__builtin_amdgcn_perm(0u, x, order));
+            c ^= ~(c >> 2) & comp;
+            // dev_pad_tail(c, L - i0 - 4 q): the bytes from the window's end on are PAD (a 64-bit shift, so that 32 clears the word)
+            const int keep = min(max(n8 - 32 * q, 0), 32);
+            const uint32_t pad = (uint32_t)(0xFFFFFFFFull << keep);
+            out[q] = __builtin_amdgcn_bitop3_b32(c, 0x07070707u, pad, 0xD8u);
         }
-        win2[e * WIN2_WORDS + chunk] = p;
+    }
+    if (!lazy_bytes) {
+        uint4* __restrict__ to = reinterpret_cast<uint4*>(win + e * WIN_STRIDE + part * PACK_CODES);
+#pragma unroll
+        for (int h = 0; h < NW / 4; ++h) to[h] = make_uint4(out[4 * h], out[4 * h + 1], out[4 * h + 2], out[4 * h + 3]);
+    }
+    if (win2) {                  // code i of a 16-code chunk in bits 2 i, 2 i + 1 of its dword
+        uint32_t p[NW / 4];
+#pragma unroll
+        for (int h = 0; h < NW / 4; ++h) {
+            p[h] = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                uint32_t t = out[4 * h + q] & 0x03030303u;
+                t = (t | (t >> 6)) & 0x000F000Fu;
+                t = (t | (t >> 12)) & 0xFFu;
+                p[h] |= t << (8 * q);
+            }
+        }
+        *reinterpret_cast<uint2*>(win2 + e * WIN2_WORDS + part * (PACK_CODES / 16)) = make_uint2(p[0], p[1]);
     }
     if (wspec) {                 // a letter outside A, C, G, T (codes 4, 5, 6; 7 is padding): the window stays off the bit-sliced path
         uint32_t spec = 0;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < NW; ++q) {
             const uint32_t t = out[q] & 0x07070707u;
             spec |= (t >> 2) & ~(t & (t >> 1) & (t >> 2)) & 0x01010101u;
         }

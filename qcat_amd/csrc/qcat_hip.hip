@@ -1006,8 +1006,6 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
     g_jit = kd;
     c->packed.prepared = false; c->packed.abs_zeroed = 0; c->packed.redo_zeroed = false;
     if (resume_kit_mask < 0) {
-        uint64_t threads = (uint64_t)n_ends * (WIN_STRIDE / 16);
-        uint32_t blocks = (uint32_t)((threads + 255) / 256);
         HIPCHK(packed_fill(c->wspec, 0, n_ends, c->stream));
         c->packed.abs_ready = 0;
         if (g_fill_defer && use_packed && hk.mode != QCAT_MODE_SIMPLE) {
@@ -1041,8 +1039,11 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
                         !opt_on(QO_NO_STATIC_ADAPTER) && !opt_on(QO_EAGER_BYTES);
             for (int t = 0; t < hk.nt && lazy; ++t) lazy = hk.tpl[t].static_kernel >= 0;
             c->packed.lazy = lazy;
-            hipLaunchKernelGGL(k_pack_windows, dim3(blocks), dim3(256), 0, c->stream,
-                               b->bases, b->offsets, n, ends, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0);
+            const uint32_t pack_blocks = (uint32_t)((n_ends + PACK_WINDOWS - 1) / PACK_WINDOWS);
+            if (ends == 2) hipLaunchKernelGGL(k_pack_windows<2>, dim3(pack_blocks), dim3(PACK_THREADS), 0, c->stream,
+                                              b->bases, b->offsets, n, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0);
+            else hipLaunchKernelGGL(k_pack_windows<1>, dim3(pack_blocks), dim3(PACK_THREADS), 0, c->stream,
+                                    b->bases, b->offsets, n, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0);
             if (lazy) hipLaunchKernelGGL(k_expand_special, dim3((uint32_t)((n_ends + 255) / 256)), dim3(256), 0, c->stream,
                                          b->bases, b->offsets, n, ends, hk.max_align, c->wspec, c->win);
         }
