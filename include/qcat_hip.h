@@ -415,6 +415,12 @@ int qcat_ctx_barcode_bitslice_tiles(qcat_ctx* ctx, uint32_t out[3]);
  * qcat_scan_sequences, the pairs of qcat_sg_align (n without statistics and within QCAT_HIP_WAVE_MAX; 0 with statistics, under QCAT_HIP_NO_TINY=1 and
  * for gap costs beyond the kernels' range); 0: the call took another path; -1: null context.  Tests and diagnostics. */
 int64_t qcat_ctx_tiny_ends(const qcat_ctx* ctx);
+/* Diagnostics of the front end of the context's latest scan of the read ends (extract_align_sequence + revcomp,
+ * qcat/scanner_base.py:223-244, and the letter planes of the bit-sliced adapter scan, csrc/kernels_abs.inc): out[0] = read ends
+ * whose windows and letter planes one kernel made in one pass over the reads (big batches of kits with a bit-sliced adapter
+ * plan), 0 when the windows were packed alone; out[1] = read ends per workgroup of that kernel, whatever the latest scan took.
+ * Tests and diagnostics. */
+int qcat_ctx_fused_front(const qcat_ctx* ctx, uint32_t out[2]);
 /* Reads of the context's latest --detect-middle scan (BarcodeScanner.scan_middle inside detect_barcode, qcat/scanner_base.py:479-519,
  * :593-595) whose interior ran on the one-wave-per-alignment kernels: interiors beyond what the packed interior scan takes (more
  * than 16 384 letters).  Synchronises the context's stream.  Tests and diagnostics. */

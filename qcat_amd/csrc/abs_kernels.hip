@@ -18,17 +18,22 @@ extern "C" void qcat_abs_launch_planes(unsigned n_tiles, void* stream, const uin
                            static_cast<uint2*>(planes), valid, need128, tile_any);
 }
 
-// the same with the windows packed in the same pass (k_pack_planes): reads -> win / wlen / wspec AND planes / valid / flags
-extern "C" void qcat_abs_launch_pack_planes(unsigned n_tiles, void* stream, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads, int ends,
-                                            uint8_t* win, int32_t* wlen, uint8_t* wspec, uint32_t n_ends, int rows, void* planes, uint32_t* valid,
-                                            uint8_t* need128, uint32_t* tile_any) {
-    const qk::AbsPackSrc ps{bases, offsets, n_reads, ends};
-    if (rows == 150)
-        hipLaunchKernelGGL(qk::k_pack_planes<150>, dim3(n_tiles), dim3(qk::ABS_PLANE_WAVES * 64), 0, static_cast<hipStream_t>(stream), ps, win, wlen, wspec, n_ends, rows,
-                           static_cast<uint2*>(planes), valid, need128, tile_any);
+// windows and planes in one pass (k_pack_planes): reads -> win2 / wlen / wspec (and byte windows unless lazy) AND planes /
+// valid / flags.  Returns the read ends per workgroup; n_reads == 0: only asks
+extern "C" unsigned qcat_abs_launch_pack_planes(void* stream, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads, int ends, int rows,
+                                                uint8_t* win, int32_t* wlen, uint8_t* wspec, uint32_t* win2, int lazy_bytes,
+                                                void* planes, uint32_t* valid, uint8_t* need128, uint32_t* tile_any) {
+    if (n_reads == 0) return qk::PP_ENDS;
+    const uint64_t n_ends = (uint64_t)n_reads * (uint64_t)ends;
+    const unsigned tiles = (unsigned)((n_ends + qk::ABS_TILE - 1) / qk::ABS_TILE);
+    const dim3 grid(tiles * (qk::ABS_TILE / qk::PP_ENDS)), block(qk::PP_THREADS);
+    if (ends == 2)
+        hipLaunchKernelGGL(qk::k_pack_planes<2>, grid, block, 0, static_cast<hipStream_t>(stream), bases, offsets, n_reads, rows, win, wlen, wspec, win2,
+                           lazy_bytes, static_cast<uint2*>(planes), valid, need128, tile_any);
     else
-        hipLaunchKernelGGL(qk::k_pack_planes<0>, dim3(n_tiles), dim3(qk::ABS_PLANE_WAVES * 64), 0, static_cast<hipStream_t>(stream), ps, win, wlen, wspec, n_ends, rows,
-                           static_cast<uint2*>(planes), valid, need128, tile_any);
+        hipLaunchKernelGGL(qk::k_pack_planes<1>, grid, block, 0, static_cast<hipStream_t>(stream), bases, offsets, n_reads, rows, win, wlen, wspec, win2,
+                           lazy_bytes, static_cast<uint2*>(planes), valid, need128, tile_any);
+    return qk::PP_ENDS;
 }
 
 // kind 0: fused two-template plan `id` (g_static_fused), kind 1: single-template plan `id` (g_static_templates); kind 2: the

@@ -65,14 +65,8 @@ __device__ __forceinline__ void abs_static_for(F&& f) {
     if constexpr (I < N) { f(AbsIC<I>{}); abs_static_for<I + 1, N>(f); }
 }
 
-// PACK = true: the kernel is k_pack_windows as well (kernels_common.inc: reads -> packed code windows, wlen, wspec) -- the
-// slice's windows are built here, written to `win` for the barcode phase and used from the LDS without a second trip
-// through HBM (k_pack_windows + k_abs_planes: 1.62 + 0.95 ms per 10 M reads; fused: see DESIGN.md 3.2a).
-struct AbsPackSrc { const uint8_t* bases; const uint64_t* offsets; uint32_t n_reads; int32_t ends; };
-
-template <int ROWS, bool PACK>
-__device__ __forceinline__ void abs_planes_body(AbsPackSrc ps, uint8_t* __restrict__ win_out, int32_t* __restrict__ wlen_out, uint8_t* __restrict__ wspec_out,
-                                                const uint32_t* __restrict__ win2, const int32_t* __restrict__ wlen, const uint8_t* __restrict__ wspec,
+template <int ROWS>
+__device__ __forceinline__ void abs_planes_body(const uint32_t* __restrict__ win2, const int32_t* __restrict__ wlen, const uint8_t* __restrict__ wspec,
                                                 uint32_t n_ends, int rows_rt, uint2* __restrict__ planes, uint32_t* __restrict__ valid,
                                                 uint8_t* __restrict__ need128, uint32_t* __restrict__ tile_any) {
     const int rows = ROWS > 0 ? ROWS : rows_rt;
@@ -80,7 +74,7 @@ __device__ __forceinline__ void abs_planes_body(AbsPackSrc ps, uint8_t* __restri
     const uint32_t tile = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = uni((int)(threadIdx.x >> 6));
     uint4* __restrict__ dst = reinterpret_cast<uint4*>(planes + (size_t)tile * rows * 64);      // [row][slice]: 16 bytes
-    __shared__ uint4 s_win[ABS_PLANE_WAVES * 64 * (PACK ? WIN_STRIDE / 16 : 3)];     // per wave: the 64 windows of the slice in hand
+    __shared__ uint4 s_win[ABS_PLANE_WAVES * 64 * 3];                                // per wave: the 64 windows of the slice in hand
     bool any = false;
     // four slices at a time: row r's words of slice k go to lane r & 63 of acc[r >> 6][k] (v_writelane), and after the
     // fourth slice every lane stores the 64 bytes of its rows -- whole lines (16-byte pieces were written back one by
@@ -104,65 +98,20 @@ __device__ __forceinline__ void abs_planes_body(AbsPackSrc ps, uint8_t* __restri
             const uint32_t e = tile * ABS_TILE + (uint32_t)sl * 64u + (uint32_t)lane;
             const bool in = e < n_ends;
             const uint32_t ec = in ? e : n_ends - 1;
-            uint4* __restrict__ mine = s_win + (size_t)wave * 64 * (PACK ? WIN_STRIDE / 16 : 3);
-            bool ok;
-            if constexpr (PACK) {
-                // the slice's 640 (read end, 16-code chunk) items, consecutive items to consecutive lanes: the stores to `win`
-                // are one contiguous kilobyte per instruction, exactly as k_pack_windows writes them
-                const uint32_t e0 = tile * ABS_TILE + (uint32_t)sl * 64u;
-                if (e0 >= n_ends) { if (lane < 2) valid[(size_t)tile * 64 + 2 * sl + lane] = 0u; continue; }
-#pragma unroll
-                for (int c = 0; c < WIN_STRIDE / 16; ++c) {
-                    const uint32_t item = (uint32_t)c * 64u + (uint32_t)lane, el = item / (WIN_STRIDE / 16), chunk = item % (WIN_STRIDE / 16);
-                    const uint32_t ee = e0 + el;
-                    uint32_t out[4] = {0x07070707u, 0x07070707u, 0x07070707u, 0x07070707u};
-                    if (ee < n_ends) {
-                        const uint64_t r = ee / (uint32_t)ps.ends;
-                        const int side = (int)(ee % (uint32_t)ps.ends);
-                        const uint64_t beg = ps.offsets[r], end = ps.offsets[r + 1], len = end - beg;
-                        const int L = len < (uint64_t)rows ? (int)len : rows;
-                        if (chunk == 0) wlen_out[ee] = L;
-                        dev_window_codes16(ps.bases + beg, ps.bases + end, side, (int)chunk * 16, L, out);
-                        *reinterpret_cast<uint4*>(win_out + (size_t)ee * WIN_STRIDE + chunk * 16) = make_uint4(out[0], out[1], out[2], out[3]);
-                        uint32_t spec = 0;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) { const uint32_t t = out[q] & 0x07070707u; spec |= (t >> 2) & ~(t & (t >> 1) & (t >> 2)) & 0x01010101u; }
-                        if (spec) wspec_out[ee] = 1;
-                    }
-                    mine[item] = make_uint4(out[0], out[1], out[2], out[3]);
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                // eligibility from the lane's own window in the LDS: full length (no PAD code 7 in the first `rows` codes)
-                // and plain letters (no code 4, 5, 6)
-                u32 odd = 0;
-                {
-                    const u32* __restrict__ roww = reinterpret_cast<const u32*>(mine + lane * (WIN_STRIDE / 16));
-                    for (int w = 0; w < (rows + 3) / 4; ++w) {
-                        u32 t = roww[w];
-                        if (w == rows / 4 && (rows & 3)) t &= (1u << (8 * (rows & 3))) - 1u;      // codes beyond the window are PAD anyway
-                        odd |= t & 0x04040404u;
-                    }
-                }
-                ok = in && odd == 0;
-            } else {
-                ok = in && wlen[ec] == rows && !wspec[ec];
-            }
+            uint4* __restrict__ mine = s_win + (size_t)wave * 64 * 3;
+            const bool ok = in && wlen[ec] == rows && !wspec[ec];
             const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
             const unsigned long long badm = __builtin_amdgcn_ballot_w64(in && !ok);
             if (lane < 2) valid[(size_t)tile * 64 + 2 * sl + lane] = (uint32_t)(lane ? okm >> 32 : okm);
             if (badm != 0 && lane == 0) need128[(tile * ABS_TILE + (uint32_t)sl * 64u) / PK_TILE] = 1;
             if (okm == 0) continue;                                 // nothing of this slice is kept: its planes stay zero
             any4 = true;
-            // the slice's 64 windows are 10 240 contiguous bytes: every lane loads ten consecutive 16-byte pieces of that
-            // block (one coalesced kilobyte per instruction) into the wave's LDS area and reads its own window back from
-            // there -- a lane fetching its own 160-byte row touches 64 different cache lines per instruction (1.9 ms for
-            // the 3.3 GB of a 10 M-read batch)
-            uint4 img[WIN_STRIDE / 16];
-            u32 img2[WIN2_WORDS];                                   // !PACK: the lane's window at two bits per code (k_pack_windows: win2)
-            if constexpr (!PACK) {
+            u32 img2[WIN2_WORDS];                                   // the lane's window at two bits per code (k_pack_windows: win2)
+            {
                 // the slice's 64 windows are 2 560 contiguous bytes at two bits per code: every lane loads ten dwords of that
                 // block (a coalesced 256 bytes per instruction) into the wave's LDS area and reads its own window back from
-                // there.  (The byte windows, 10 240 bytes per slice, were 3.3 GB of this kernel's 4.1 GB per 10 M reads)
+                // there.  (The byte windows, 10 240 bytes per slice, were 3.3 GB of this kernel's 4.1 GB per 10 M reads; a lane
+                // fetching its own row touches 64 different cache lines per instruction)
                 const uint32_t e0 = tile * ABS_TILE + (uint32_t)sl * 64u;
                 const uint32_t* __restrict__ src = win2 + (size_t)e0 * WIN2_WORDS;
                 const size_t lim = ((size_t)n_ends - e0) * WIN2_WORDS;                  // dwords of this slice that exist
@@ -176,24 +125,12 @@ __device__ __forceinline__ void abs_planes_body(AbsPackSrc ps, uint8_t* __restri
 #pragma unroll
                 for (int c = 0; c < WIN2_WORDS; ++c) img2[c] = mine2[lane * WIN2_WORDS + c];
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            } else {
-#pragma unroll
-                for (int c = 0; c < WIN_STRIDE / 16; ++c) img[c] = mine[lane * (WIN_STRIDE / 16) + c];
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
             abs_static_for<0, NG * 64 < WIN_STRIDE ? NG * 64 : WIN_STRIDE>([&](auto R_) {
                 constexpr int r = decltype(R_)::value, c = r >> 4, q = r & 15;
                 if (ROWS > 0 ? r < ROWS : r < rows) {
-                    unsigned long long m1, m0;
-                    if constexpr (!PACK) {
-                        m1 = __builtin_amdgcn_ballot_w64((img2[c] & (2u << (2 * q))) != 0);
-                        m0 = __builtin_amdgcn_ballot_w64((img2[c] & (1u << (2 * q))) != 0);
-                    } else {
-                        const uint4 ch = img[c];
-                        const u32 w = (q >> 2) == 0 ? ch.x : ((q >> 2) == 1 ? ch.y : ((q >> 2) == 2 ? ch.z : ch.w));
-                        m1 = __builtin_amdgcn_ballot_w64((w & (2u << (8 * (q & 3)))) != 0);
-                        m0 = __builtin_amdgcn_ballot_w64((w & (1u << (8 * (q & 3)))) != 0);
-                    }
+                    const unsigned long long m1 = __builtin_amdgcn_ballot_w64((img2[c] & (2u << (2 * q))) != 0);
+                    const unsigned long long m0 = __builtin_amdgcn_ballot_w64((img2[c] & (1u << (2 * q))) != 0);
                     abs_writelane<(r & 63)>((u32)m1, acc[r >> 6][k][0]);
                     abs_writelane<(r & 63)>((u32)m0, acc[r >> 6][k][1]);
                     abs_writelane<(r & 63)>((u32)(m1 >> 32), acc[r >> 6][k][2]);
@@ -221,17 +158,82 @@ __global__ void __launch_bounds__(ABS_PLANE_WAVES * 64)
 k_abs_planes(const uint32_t* __restrict__ win2, const int32_t* __restrict__ wlen, const uint8_t* __restrict__ wspec,
              uint32_t n_ends, int rows_rt, uint2* __restrict__ planes, uint32_t* __restrict__ valid,
              uint8_t* __restrict__ need128, uint32_t* __restrict__ tile_any) {
-    abs_planes_body<ROWS, false>(AbsPackSrc{nullptr, nullptr, 0, 1}, nullptr, nullptr, nullptr, win2, wlen, wspec, n_ends, rows_rt, planes, valid, need128, tile_any);
+    abs_planes_body<ROWS>(win2, wlen, wspec, n_ends, rows_rt, planes, valid, need128, tile_any);
 }
 
-// k_pack_windows + k_abs_planes in one pass (big batches of kits with a bit-sliced adapter plan): replaces k_pack_windows
-// (kernels_common.inc; extract_align_sequence + revcomp, qcat/scanner_base.py:223-244, utils.py:20-21) for the batch
-template <int ROWS>
-__global__ void __launch_bounds__(ABS_PLANE_WAVES * 64)
-k_pack_planes(AbsPackSrc ps, uint8_t* __restrict__ win, int32_t* __restrict__ wlen, uint8_t* __restrict__ wspec,
-              uint32_t n_ends, int rows_rt, uint2* __restrict__ planes, uint32_t* __restrict__ valid,
-              uint8_t* __restrict__ need128, uint32_t* __restrict__ tile_any) {
-    abs_planes_body<ROWS, true>(ps, win, wlen, wspec, nullptr, nullptr, nullptr, n_ends, rows_rt, planes, valid, need128, tile_any);
+// ---------------------------------------------------------------------------------------------
+// k_pack_planes<ENDS>: k_pack_windows and k_abs_planes in one pass over the reads (big batches of kits with a bit-sliced
+// adapter plan).  A workgroup takes PP_ENDS consecutive read ends, a quarter of a plane tile.
+//   pack       every thread is a thread of k_pack_windows (dev_pack_part, kernels_common.inc: 32 codes, nine dwords in
+//              flight; win2 / wlen / wspec and the byte windows leave exactly as from that kernel), PP_ITER items each; the
+//              window's ten dwords also go to the LDS, and an end that stays off the path sets its bit in s_bad.
+//   transpose  after the barrier one thread takes 32 read ends x one window dword from the LDS, transposes the 32 x 32 bit
+//              matrix in registers (bs_transpose32, bs_core.h) and stores the plane words of its sixteen rows; consecutive
+//              lanes hold consecutive groups of 32 ends, so a row's stores are 128 contiguous bytes.  LDS layout: ten
+//              dwords per end, four dwords of padding per group of 32 ends -- lane (group g, dword d) reads bank
+//              4 g + d + 10 i for end i of its group, the 64 lanes of a wave (16 g x 4 d) 64 different banks.
+//   flags      valid, need128 and tile_any from s_bad and the read-end count: the values k_abs_planes derives from wlen and
+//              wspec.  Unlike that kernel, the planes of a slice without any valid end are written too (nobody reads them:
+//              their keep masks are zero).
+// The grid covers whole tiles: a workgroup past the last read end only clears its keep masks.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t PP_ENDS = 512;                                        // read ends per workgroup
+constexpr uint32_t PP_THREADS = 640;
+constexpr uint32_t PP_ITER = PP_ENDS * PACK_PARTS / PP_THREADS;          // pack items per thread
+constexpr uint32_t PP_GROUPS = PP_ENDS / 32;                             // plane lanes per workgroup
+constexpr uint32_t PP_GSTRIDE = 32 * WIN2_WORDS + 4;                     // dwords of a group of 32 ends in the LDS
+static_assert(PP_ITER * PP_THREADS == PP_ENDS * PACK_PARTS && PP_THREADS % PACK_PARTS == 0 && ABS_TILE % PP_ENDS == 0 && PP_ENDS % PK_TILE == 0 &&
+              PP_GROUPS * WIN2_WORDS + PP_GROUPS <= PP_THREADS && PACK_CODES == 32, "k_pack_planes: the item arithmetic below");
+
+template <int ENDS>
+__global__ void __launch_bounds__(PP_THREADS)
+k_pack_planes(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offsets, uint32_t n_reads, int max_align,
+              uint8_t* __restrict__ win, int32_t* __restrict__ wlen, uint8_t* __restrict__ wspec, uint32_t* __restrict__ win2, int lazy_bytes,
+              uint2* __restrict__ planes, uint32_t* __restrict__ valid, uint8_t* __restrict__ need128, uint32_t* __restrict__ tile_any) {
+    __shared__ __attribute__((aligned(8))) u32 s_win[PP_GROUPS * PP_GSTRIDE];
+    __shared__ u32 s_bad[PP_GROUPS];
+    const uint64_t n_ends = (uint64_t)n_reads * ENDS;
+    const uint64_t e0 = (uint64_t)blockIdx.x * PP_ENDS;
+    const uint32_t tile = (uint32_t)(e0 / ABS_TILE), lane0 = (uint32_t)(e0 % ABS_TILE) / 32u;
+    if (e0 >= n_ends) {
+        if (threadIdx.x < PP_GROUPS) valid[(size_t)tile * 64 + lane0 + threadIdx.x] = 0u;
+        return;
+    }
+    if (threadIdx.x < PP_GROUPS) s_bad[threadIdx.x] = 0u;
+    __syncthreads();
+    {
+        const uint32_t wl = threadIdx.x / PACK_PARTS, part = threadIdx.x - wl * PACK_PARTS;
+#pragma unroll
+        for (uint32_t it = 0; it < PP_ITER; ++it) {
+            const uint32_t el = it * (PP_THREADS / PACK_PARTS) + wl;
+            const uint64_t e = e0 + el;
+            uint32_t p[PACK_CODES / 16] = {0u, 0u};                      // (past the last read end: zero planes, as k_abs_planes reads them)
+            if (e < n_ends && dev_pack_part<ENDS>(bases, offsets, max_align, e, part, win, wlen, wspec, win2, lazy_bytes, p))
+                atomicOr(&s_bad[el >> 5], 1u << (el & 31u));
+            *reinterpret_cast<uint2*>(&s_win[(el >> 5) * PP_GSTRIDE + (el & 31u) * WIN2_WORDS + part * (PACK_CODES / 16)]) = make_uint2(p[0], p[1]);
+        }
+    }
+    __syncthreads();
+    const int rows = max_align;
+    if (threadIdx.x < PP_GROUPS * WIN2_WORDS) {
+        const uint32_t g = threadIdx.x % PP_GROUPS, d = threadIdx.x / PP_GROUPS;
+        u32 v[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) v[i] = s_win[g * PP_GSTRIDE + (uint32_t)i * WIN2_WORDS + d];
+        bs_transpose32(v);                                               // v[2 q + 1], v[2 q]: planes c1, c0 of code 16 d + q, bit i = end i of the group
+        uint2* __restrict__ dst = planes + ((size_t)tile * rows + d * 16u) * 64 + lane0 + g;
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if ((int)(d * 16u) + q < rows) dst[(size_t)q * 64] = make_uint2(v[2 * q + 1], v[2 * q]);
+    } else if (threadIdx.x < PP_GROUPS * WIN2_WORDS + PP_GROUPS) {
+        const uint32_t g = threadIdx.x - PP_GROUPS * WIN2_WORDS;
+        const uint64_t eg = e0 + g * 32u;
+        const u32 in = eg >= n_ends ? 0u : (n_ends - eg >= 32u ? 0xFFFFFFFFu : (1u << (uint32_t)(n_ends - eg)) - 1u);
+        const u32 ok = in & ~s_bad[g];
+        valid[(size_t)tile * 64 + lane0 + g] = ok;
+        if (in & ~ok) need128[eg / PK_TILE] = 1;
+        if (ok) tile_any[tile] = 1;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -136,21 +136,15 @@ constexpr uint32_t PACK_PARTS = WIN_STRIDE / PACK_CODES;                 // 5
 constexpr uint32_t PACK_WINDOWS = 64;
 constexpr uint32_t PACK_THREADS = PACK_WINDOWS * PACK_PARTS;
 
+// One thread's share of a window: the 32 codes from position part * 32 on of read end e, stored exactly as k_pack_windows
+// stores them (the body of that kernel; k_pack_planes, kernels_abs.inc, is the second caller).  p: the codes at two bits
+// each, whether or not win2 is given; the return value: this part holds a letter outside A, C, G, T, or the window is shorter
+// than max_align -- the end stays off the bit-sliced adapter path.
 template <int ENDS>
-__global__ void __launch_bounds__(PACK_THREADS)
-k_pack_windows(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offsets,
-               uint32_t n_reads, int max_align,
-               uint8_t* __restrict__ win, int32_t* __restrict__ wlen, uint8_t* __restrict__ wspec,
-               uint32_t* __restrict__ win2 /* two bits per code beside the bytes (WIN2_WORDS dwords per window; meaningful for
-                                              windows of plain A, C, G, T): what the bit-sliced kernels read; or null */,
-               int lazy_bytes = 0 /* 1: no byte windows here -- k_expand_special writes those of the flagged ends, every reader
-                                     expands the others from win2 (dev_window16): 3.3 GB less to write per 10 M reads */) {
-    static_assert(ENDS == 1 || ENDS == 2, "one or two windows per read");
-    static_assert(PACK_PARTS == 5 && PACK_PARTS * PACK_CODES == WIN_STRIDE && PACK_THREADS < 1000, "threadIdx.x / 5 below is (x * 205) >> 10");
-    const uint32_t wl = (threadIdx.x * 205u) >> 10;
-    const uint32_t part = threadIdx.x - wl * PACK_PARTS;
-    const uint64_t e = (uint64_t)blockIdx.x * PACK_WINDOWS + wl;
-    if (e >= (uint64_t)n_reads * ENDS) return;
+__device__ __forceinline__ bool dev_pack_part(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offsets, int max_align,
+                                              uint64_t e, uint32_t part,
+                                              uint8_t* __restrict__ win, int32_t* __restrict__ wlen, uint8_t* __restrict__ wspec,
+                                              uint32_t* __restrict__ win2, int lazy_bytes, uint32_t (&p)[PACK_CODES / 16]) {
     const uint64_t r = ENDS == 2 ? e >> 1 : e;
     const uint32_t side = ENDS == 2 ? (uint32_t)e & 1u : 0u;
     uint64_t beg = offsets[r], end = offsets[r + 1];
@@ -185,23 +179,21 @@ k_pack_windows(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ o
 #pragma unroll
         for (int h = 0; h < NW / 4; ++h) to[h] = make_uint4(out[4 * h], out[4 * h + 1], out[4 * h + 2], out[4 * h + 3]);
     }
-    if (win2) {                  // code i of a 16-code chunk in bits 2 i, 2 i + 1 of its dword
-        uint32_t p[NW / 4];
+    // code i of a 16-code chunk in bits 2 i, 2 i + 1 of its dword
 #pragma unroll
-        for (int h = 0; h < NW / 4; ++h) {
-            p[h] = 0;
+    for (int h = 0; h < NW / 4; ++h) {
+        p[h] = 0;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint32_t t = out[4 * h + q] & 0x03030303u;
-                t = (t | (t >> 6)) & 0x000F000Fu;
-                t = (t | (t >> 12)) & 0xFFu;
-                p[h] |= t << (8 * q);
-            }
+        for (int q = 0; q < 4; ++q) {
+            uint32_t t = out[4 * h + q] & 0x03030303u;
+            t = (t | (t >> 6)) & 0x000F000Fu;
+            t = (t | (t >> 12)) & 0xFFu;
+            p[h] |= t << (8 * q);
         }
-        *reinterpret_cast<uint2*>(win2 + e * WIN2_WORDS + part * (PACK_CODES / 16)) = make_uint2(p[0], p[1]);
     }
+    if (win2) *reinterpret_cast<uint2*>(win2 + e * WIN2_WORDS + part * (PACK_CODES / 16)) = make_uint2(p[0], p[1]);
+    uint32_t spec = 0;
     if (wspec) {                 // a letter outside A, C, G, T (codes 4, 5, 6; 7 is padding): the window stays off the bit-sliced path
-        uint32_t spec = 0;
 #pragma unroll
         for (int q = 0; q < NW; ++q) {
             const uint32_t t = out[q] & 0x07070707u;
@@ -209,6 +201,26 @@ k_pack_windows(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ o
         }
         if (spec) wspec[e] = 1;
     }
+    return spec != 0 || L != max_align;
+}
+
+template <int ENDS>
+__global__ void __launch_bounds__(PACK_THREADS)
+k_pack_windows(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ offsets,
+               uint32_t n_reads, int max_align,
+               uint8_t* __restrict__ win, int32_t* __restrict__ wlen, uint8_t* __restrict__ wspec,
+               uint32_t* __restrict__ win2 /* two bits per code beside the bytes (WIN2_WORDS dwords per window; meaningful for
+                                              windows of plain A, C, G, T): what the bit-sliced kernels read; or null */,
+               int lazy_bytes = 0 /* 1: no byte windows here -- k_expand_special writes those of the flagged ends, every reader
+                                     expands the others from win2 (dev_window16): 3.3 GB less to write per 10 M reads */) {
+    static_assert(ENDS == 1 || ENDS == 2, "one or two windows per read");
+    static_assert(PACK_PARTS == 5 && PACK_PARTS * PACK_CODES == WIN_STRIDE && PACK_THREADS < 1000, "threadIdx.x / 5 below is (x * 205) >> 10");
+    const uint32_t wl = (threadIdx.x * 205u) >> 10;
+    const uint32_t part = threadIdx.x - wl * PACK_PARTS;
+    const uint64_t e = (uint64_t)blockIdx.x * PACK_WINDOWS + wl;
+    if (e >= (uint64_t)n_reads * ENDS) return;
+    uint32_t p[PACK_CODES / 16];
+    (void)dev_pack_part<ENDS>(bases, offsets, max_align, e, part, win, wlen, wspec, win2, lazy_bytes, p);
 }
 
 // the byte windows of the read ends k_pack_windows flagged (a letter outside A, C, G, T): the only ones a lazy scan has

@@ -76,7 +76,7 @@
     X(NO_SLIM, "1: the 60-byte per-end records instead of the packed result arrays") \
     X(NO_FILL_MERGE, "1: one fill launch per buffer instead of k_fill_multi") \
     X(EAGER_BYTES, "1: byte windows for every read end, not only for those with a letter outside A, C, G, T") \
-    X(PACK_PLANES, "1: letter planes built inside the window kernel (measured slower)") \
+    X(PACK_PLANES, "0: windows and adapter letter planes of a big batch as two kernels (k_pack_windows, k_abs_planes) instead of one (k_pack_planes)") \
     X(FIN_BLOCKS, "blocks of k_finalize") \
     X(FINISH_BLOCKS, "blocks of k_adapter_finish") \
     X(ABS_NO_SPLIT, "1: medium batches keep the fused two-template plan") \

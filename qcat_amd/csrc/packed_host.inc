@@ -10,9 +10,9 @@
 // the bit-sliced adapter kernels live in a translation unit of their own (abs_kernels.hip, kernels_abs.inc)
 extern "C" void qcat_abs_launch_planes(unsigned n_tiles, void* stream, const uint32_t* win2, const int32_t* wlen, const uint8_t* wspec,
                                        uint32_t n_ends, int rows, void* planes, uint32_t* valid, uint8_t* need128, uint32_t* tile_any);
-extern "C" void qcat_abs_launch_pack_planes(unsigned n_tiles, void* stream, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads, int ends,
-                                            uint8_t* win, int32_t* wlen, uint8_t* wspec, uint32_t n_ends, int rows, void* planes, uint32_t* valid,
-                                            uint8_t* need128, uint32_t* tile_any);
+extern "C" unsigned qcat_abs_launch_pack_planes(void* stream, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads, int ends, int rows,
+                                                uint8_t* win, int32_t* wlen, uint8_t* wspec, uint32_t* win2, int lazy_bytes,
+                                                void* planes, uint32_t* valid, uint8_t* need128, uint32_t* tile_any);
 extern "C" int qcat_abs_launch(int kind, int id, unsigned grid, void* stream, const void* args);
 
 namespace qk {

@@ -532,6 +532,7 @@ struct qcat_ctx {
     // the handful-of-reads path (kernels_tiny.inc): per read end the templates' (raw, end) and the barcodes' raw scores
     int32_t* tiny_tpl = nullptr; int16_t* tiny_sc = nullptr; size_t cap_tiny = 0, cap_tiny_ends = 0;
     uint32_t last_tiny_ends = 0;                   // read ends the last scan put on that path (0: another path)
+    uint32_t last_fused_ends = 0;                  // read ends whose windows and letter planes the last scan made in one kernel (k_pack_planes)
     int32_t* tiny_simple = nullptr; size_t cap_tiny_simple = 0;    // simple kits on qcat_scan_sequences: (raw, end_query) per (sequence, barcode) of a piece
     // simple mode on the packed kernels (kernels_simple.inc): one (key, end) per (work unit, read end); the read ends whose best raw
     // score is 0 ([0]: their count); debug scans with rows: (raw, end) of every barcode
@@ -991,6 +992,7 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
     const bool tiny = n_ends > 0 && n_ends <= 4096 && tiny_fits && !opt_on(QO_NO_TINY) && hk.mode != QCAT_MODE_SIMPLE && resume_kit_mask < 0 &&
                       !adapter_only && !c->force_generic && hk.gap_open == hk.gap_extend;
     c->last_tiny_ends = tiny ? (uint32_t)n_ends : 0;
+    c->last_fused_ends = 0;
     if (tiny) {
         if ((rc = tiny_buffers(c, (size_t)n_ends, tiny_maxb))) return rc;
         use_packed = false;                        // (no job tables, no lazy windows: the tiny kernels read byte windows)
@@ -1012,41 +1014,39 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
             c->packed.slim = use_packed && !debug && !opt_on(QO_NO_SLIM);     // (packed_prepare sizes the slim buffers)
             if ((rc = packed_prepare(c->stream, hk, (uint32_t)n_ends, &c->packed))) { g_fill_defer = false; g_fill.n = 0; return set_err(rc, packed_last_error()); }
             c->packed.prepared = true;
-            if (!opt_on(QO_PACK_PLANES) && packed_abs_wanted(hk, (uint32_t)n_ends, true) &&
+            if (packed_abs_wanted(hk, (uint32_t)n_ends, true) &&
                 (rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) { g_fill_defer = false; g_fill.n = 0; return set_err(rc, packed_last_error()); }
         }
         HIPCHK(packed_fill_flush(c->stream));
-        if (use_packed && hk.mode != QCAT_MODE_SIMPLE && opt_on(QO_PACK_PLANES) && packed_abs_wanted(hk, (uint32_t)n_ends, true)) {
-            // (A/B switch, off by default) the windows and their letter planes in one pass (kernels_abs.inc: k_pack_planes).
-            // Measured and dropped: 5.1 ms against 1.67 + 0.85 ms for k_pack_windows + k_abs_planes on config 3 -- a wave that
-            // walks eight slices of 640 items serially is latency-bound on the offsets -> bases load chains, where
-            // k_pack_windows has one thread per item (profiles/r03_ab_pack_planes.json)
-            if ((rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
+        c->win2_valid = true;
+        // lazy byte windows (round 4): a kit whose every template runs a generated kernel reads plain windows at two
+        // bits per code everywhere (dev_window16), so the byte windows -- 3.3 of the pack kernel's 4.1 GB of stores per
+        // 10 M reads -- are written for the flagged ends only (k_expand_special; QCAT_HIP_EAGER_BYTES=1: all of them)
+        bool lazy = use_packed && hk.mode != QCAT_MODE_SIMPLE && hk.adapter_f16 && !opt_on(QO_NO_STATIC) &&
+                    !opt_on(QO_NO_STATIC_ADAPTER) && !opt_on(QO_EAGER_BYTES);
+        for (int t = 0; t < hk.nt && lazy; ++t) lazy = hk.tpl[t].static_kernel >= 0;
+        c->packed.lazy = lazy;
+        // a batch the bit-sliced adapter kernels will take: its windows and their letter planes in one pass (kernels_abs.inc:
+        // k_pack_planes), so that the windows are not read back from memory.  QCAT_HIP_PACK_PLANES=0 (A/B builds):
+        // k_pack_windows here and k_abs_planes in the adapter phase, the route of every other batch and of the vote pass of kit auto
+        if (use_packed && hk.mode != QCAT_MODE_SIMPLE && !adapter_only && opt_val(QO_PACK_PLANES, 1) != 0 && packed_abs_wanted(hk, (uint32_t)n_ends, true)) {
+            if (c->packed.abs_zeroed != (uint32_t)n_ends && (rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
             const uint32_t tiles = ((uint32_t)n_ends + ABS_TILE - 1) / ABS_TILE;
             uint32_t* cursor = reinterpret_cast<uint32_t*>(c->packed.abs_flags);
             uint32_t* tile_any = cursor + MAX_T;
-            qcat_abs_launch_pack_planes(tiles, c->stream, b->bases, b->offsets, n, ends, c->win, c->wlen, c->wspec, (uint32_t)n_ends, hk.max_align,
-                                        c->packed.abs_planes, c->packed.abs_valid, reinterpret_cast<uint8_t*>(tile_any + tiles), tile_any);
+            (void)qcat_abs_launch_pack_planes(c->stream, b->bases, b->offsets, n, ends, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0,
+                                              c->packed.abs_planes, c->packed.abs_valid, reinterpret_cast<uint8_t*>(tile_any + tiles), tile_any);
             c->packed.abs_ready = (uint32_t)n_ends;
-            c->win2_valid = false;                       // (that kernel does not make the two-bit copy)
-            c->packed.lazy = false;
+            c->last_fused_ends = (uint32_t)n_ends;
         } else {
-            c->win2_valid = true;
-            // lazy byte windows (round 4): a kit whose every template runs a generated kernel reads plain windows at two
-            // bits per code everywhere (dev_window16), so the byte windows -- 3.3 of the pack kernel's 4.1 GB of stores per
-            // 10 M reads -- are written for the flagged ends only (k_expand_special; QCAT_HIP_EAGER_BYTES=1: all of them)
-            bool lazy = use_packed && hk.mode != QCAT_MODE_SIMPLE && hk.adapter_f16 && !opt_on(QO_NO_STATIC) &&
-                        !opt_on(QO_NO_STATIC_ADAPTER) && !opt_on(QO_EAGER_BYTES);
-            for (int t = 0; t < hk.nt && lazy; ++t) lazy = hk.tpl[t].static_kernel >= 0;
-            c->packed.lazy = lazy;
             const uint32_t pack_blocks = (uint32_t)((n_ends + PACK_WINDOWS - 1) / PACK_WINDOWS);
             if (ends == 2) hipLaunchKernelGGL(k_pack_windows<2>, dim3(pack_blocks), dim3(PACK_THREADS), 0, c->stream,
                                               b->bases, b->offsets, n, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0);
             else hipLaunchKernelGGL(k_pack_windows<1>, dim3(pack_blocks), dim3(PACK_THREADS), 0, c->stream,
                                     b->bases, b->offsets, n, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0);
-            if (lazy) hipLaunchKernelGGL(k_expand_special, dim3((uint32_t)((n_ends + 255) / 256)), dim3(256), 0, c->stream,
-                                         b->bases, b->offsets, n, ends, hk.max_align, c->wspec, c->win);
         }
+        if (lazy) hipLaunchKernelGGL(k_expand_special, dim3((uint32_t)((n_ends + 255) / 256)), dim3(256), 0, c->stream,
+                                     b->bases, b->offsets, n, ends, hk.max_align, c->wspec, c->win);
         mark(c, "k_pack_windows");
     }
     if (resume_kit_mask >= 0 && g_fill_defer && use_packed && c->packed.slices_single && hk.mode != QCAT_MODE_SIMPLE) {
@@ -1215,6 +1215,14 @@ static int fetch_back(qcat_ctx* c, qcat_result* out, uint32_t n_reads, int64_t* 
 
 extern "C" void* qcat_ctx_stream(qcat_ctx* c) { return c ? (void*)c->stream : nullptr; }
 extern "C" int64_t qcat_ctx_tiny_ends(const qcat_ctx* c) { return c ? (int64_t)c->last_tiny_ends : -1; }
+// diagnostics of the latest scan's front end: out[0] = read ends whose windows and letter planes came from the one kernel
+// (k_pack_planes; 0: k_pack_windows, and k_abs_planes where the bit-sliced adapter scan ran), out[1] = read ends per workgroup of that kernel
+extern "C" int qcat_ctx_fused_front(const qcat_ctx* c, uint32_t* out) {
+    if (!c || !out) return set_err(QCAT_ERR_ARG, "null argument");
+    out[0] = c->last_fused_ends;
+    out[1] = qcat_abs_launch_pack_planes(nullptr, nullptr, nullptr, 0, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+    return 0;
+}
 // reads whose interior the latest --detect-middle scan put on the one-wave kernels (k_midw_*: interiors the packed interior scan
 // does not take); synchronises the stream; -1: null context, 0: none / the path did not run
 extern "C" int64_t qcat_ctx_middle_wave_reads(qcat_ctx* c) {
