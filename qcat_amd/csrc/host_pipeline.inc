@@ -93,11 +93,10 @@ private:
 };
 
 struct PipeStage {                     // one of the two chunk slots
-    uint8_t* pin_bases = nullptr; uint64_t* pin_offsets = nullptr; uint32_t* pin_len = nullptr;
-    uint8_t* dev_bases_alloc = nullptr; uint64_t* dev_offsets = nullptr; uint32_t* dev_len = nullptr;
-    qcat_result* pin_results = nullptr;                 // the chunk's records on their way to the caller's array
+    PinBuf<uint8_t> pin_bases; PinBuf<uint64_t> pin_offsets; PinBuf<uint32_t> pin_len;
+    DevBuf<uint8_t> dev_bases_alloc; DevBuf<uint64_t> dev_offsets; DevBuf<uint32_t> dev_len;
+    PinBuf<qcat_result> pin_results;                    // the chunk's records on their way to the caller's array
     uint32_t res_first = 0, res_count = 0;              // ... reads [res_first, res_first + res_count), 0: nothing pending
-    size_t cap_bases = 0, cap_reads = 0;
     hipEvent_t copied = nullptr, scanned = nullptr;
 };
 
@@ -111,16 +110,11 @@ static inline void pipeline_free(HostPipeline* p) {
     if (!p) return;
     delete p->pool;
     for (PipeStage& s : p->st) {
-        if (s.pin_bases) (void)hipHostFree(s.pin_bases);
-        if (s.pin_offsets) (void)hipHostFree(s.pin_offsets);
-        if (s.pin_len) (void)hipHostFree(s.pin_len);
-        if (s.pin_results) (void)hipHostFree(s.pin_results);
-        (void)hipFree(s.dev_bases_alloc); (void)hipFree(s.dev_offsets); (void)hipFree(s.dev_len);
         if (s.copied) (void)hipEventDestroy(s.copied);
         if (s.scanned) (void)hipEventDestroy(s.scanned);
     }
     if (p->copy) (void)hipStreamDestroy(p->copy);
-    delete p;
+    delete p;                          // (the stages' staging buffers free themselves)
 }
 
 }  // namespace qk

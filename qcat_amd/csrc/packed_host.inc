@@ -5,7 +5,7 @@
 // shared by the main scan (packed_scan) and the interior scan of --detect-middle (qcat_hip.hip).
 // Included by qcat_hip.hip after kernels_packed.inc (and by jit_prelude.inc for the struct layouts).
 
-#include <atomic>
+#include "dev_buf.h"
 
 // the bit-sliced adapter kernels live in a translation unit of their own (abs_kernels.hip, kernels_abs.inc)
 extern "C" void qcat_abs_launch_planes(unsigned n_tiles, void* stream, const uint32_t* win2, const int32_t* wlen, const uint8_t* wspec,
@@ -24,46 +24,39 @@ constexpr int ABS_TILE = 2048;          // read ends per tile of the bit-sliced 
 constexpr int RESUME_KIT_ON_DEVICE = 1 << 20;      // resume_kit_mask: the voted kit slot is on the device (PackedScratch::kit_slot_dev)
 
 struct PackedScratch {
-    JobTables* jt = nullptr;
-    int32_t* sorted = nullptr;
-    size_t cap_sorted = 0;
-    uint32_t* jobinfo = nullptr;       // [read end][set] region length | sort bin << 8 | start << 16 (k_adapter_finish), 0: no job
-    size_t cap_jobinfo = 0;
-    AdapterBest* bests = nullptr;
-    size_t cap_bests = 0;
+    DevBuf<JobTables> jt;              // (allocated once)
+    DevBuf<int32_t> sorted;
+    DevBuf<uint32_t> jobinfo;          // [read end][set] region length | sort bin << 8 | start << 16 (k_adapter_finish), 0: no job
+    DevBuf<AdapterBest> bests;
     int n_slices = 0;                  // slices of `bests` the last adapter phase wrote
     bool slices_single = false;        // ... each of exactly one template (kit-mask merges are possible)
-    uint8_t* tilebuf = nullptr;        // [tiles][64 lanes][160 B] LDS images of the barcode tiles
-    TileMeta* tmeta = nullptr;         // [tiles][64]
-    size_t cap_tiles = 0;
-    uint32_t* raws = nullptr;          // [tiles][bstride][64] raw barcode scores, two int16 per dword
-    size_t cap_raws = 0;
-    uint32_t* part = nullptr;          // summary mode: [tiles][part_stride][2][64] keys (kernels_packed.inc, barcode_key)
-    size_t cap_part = 0;
-    uint32_t* redo = nullptr;          // summary mode: [0] = count, [1..] = alignments whose arg-max needs the sequential rule
-    size_t cap_redo = 0;
+    DevBuf<uint8_t> tilebuf;           // [tiles][64 lanes][160 B] LDS images of the barcode tiles
+    DevBuf<TileMeta> tmeta;            // [tiles][64]
+    DevBuf<uint32_t> raws;             // [tiles][bstride][64] raw barcode scores, two int16 per dword
+    DevBuf<uint32_t> part;             // summary mode: [tiles][part_stride][2][64] keys (kernels_packed.inc, barcode_key)
+    DevBuf<uint32_t> redo;             // summary mode: [0] = count, [1..] = alignments whose arg-max needs the sequential rule
     // bit-sliced barcode kernels (kernels_bitslice.inc)
     const uint8_t* wspec = nullptr;    // per read end: letters outside A, C, G, T, N (null: no hot classes, e.g. read interiors)
     const uint8_t* win = nullptr;      // the packed windows the flags belong to
     const uint32_t* win2 = nullptr;    // ... at two bits per code (k_pack_windows)
     bool lazy = false;                 // the scan's byte windows exist for the flagged ends only (k_expand_special): readers go through dev_window16
-    BsPlan* bsplan = nullptr;
-    uint32_t* bskeys = nullptr; size_t cap_bskeys = 0;     // [chunk][sorted position]
+    DevBuf<BsPlan> bsplan;                                 // (allocated once)
+    DevBuf<uint32_t> bskeys;                               // [chunk][sorted position]
     bool bs_last = false;                                  // the latest scan planned super-tiles (qcat_ctx_barcode_bitslice_tiles)
-    uint2* bsrp = nullptr; size_t cap_bsrp = 0;            // [launch][workgroup][BS_MAX_ROWS][64]: plane pairs of the trailing columns (bs_trailing_columns)
+    DevBuf<uint2> bsrp;                                    // [launch][workgroup][BS_MAX_ROWS][64]: plane pairs of the trailing columns (bs_trailing_columns)
     // bit-sliced adapter kernels (kernels_abs.inc): letter planes of the tiles, per-lane keep masks, and one zeroed block
     // of flags per scan: [tile cursors: MAX_T u32][tile_any: n_tiles u32][need128: n_tiles * 16 bytes]
-    uint2* abs_planes = nullptr; size_t cap_abs_planes = 0;
-    uint32_t* abs_valid = nullptr; size_t cap_abs_valid = 0;
-    uint8_t* abs_flags = nullptr; size_t cap_abs_flags = 0;
+    DevBuf<uint2> abs_planes;
+    DevBuf<uint32_t> abs_valid;
+    DevBuf<uint8_t> abs_flags;
     // round 3: sorted position of every job (k_job_scatter) and the packed barcode results (index, raw score) per job that
     // the select kernels write and k_finalize reads; `slim` = this scan uses them (the main scan outside debug mode)
-    uint32_t* posof = nullptr; size_t cap_posof = 0;
-    int2* bcres = nullptr; size_t cap_bcres = 0;
+    DevBuf<uint32_t> posof;
+    DevBuf<int2> bcres;
     bool slim = false;
     // ... and one word per read end for k_finalize instead of the record (k_adapter_finish); fin_only = this pass writes it
     // (a slim scan that is not the adapter-only pass of kit auto, whose vote reads the records)
-    uint32_t* fin = nullptr; size_t cap_fin = 0;
+    DevBuf<uint32_t> fin;
     bool fin_only = false;
     uint32_t abs_ready = 0;            // read ends whose planes / flags the fused pack kernel of this scan has already made (0: none)
     uint32_t abs_zeroed = 0;           // read ends whose flag block this scan has sized and zeroed already (packed_abs_buffers ahead of the pack kernel)
@@ -103,13 +96,15 @@ static inline hipError_t packed_fill_flush(hipStream_t stream) {
     g_fill.n = 0;
     return hipGetLastError();
 }
-// every device allocation of the scan path bumps this counter: a captured graph of a kit-auto call (qcat_hip.hip:
-// scan_batch_auto_impl) holds the buffers' addresses and is dropped when anything was reallocated since its capture
-// (process-wide, not per thread: the workers of the kit-auto file loop are new threads at every call, and a counter that
-// starts at zero in each of them could match a graph captured by an earlier thread although another thread moved the buffers
-// in between; an allocation of ANY context drops every context's graph -- spurious, and safe)
-static std::atomic<uint64_t> g_alloc_gen{0};
-static inline hipError_t q_malloc(void** p, size_t bytes) { g_alloc_gen.fetch_add(1); return hipMalloc(p, bytes); }
+// the stretch of a function that collects fills (defer: as one launch; else each a memset at once): starts from an empty
+// list and leaves an empty list and a cleared flag behind on every way out, so a return between a packed_fill and its
+// packed_fill_flush drops the queued fills instead of handing them to the thread's next scan
+struct FillScope {
+    explicit FillScope(bool defer) { g_fill.n = 0; g_fill_defer = defer; }
+    ~FillScope() { g_fill.n = 0; g_fill_defer = false; }
+    FillScope(const FillScope&) = delete;
+    FillScope& operator=(const FillScope&) = delete;
+};
 static inline const char* packed_last_error() { return g_packed_err.c_str(); }
 // a failed launch of a run-time generated kernel (jit_launch, qcat_hip.hip) is recorded here and turned
 // into the scan's status by the phase that issued it
@@ -159,36 +154,8 @@ static inline void packed_streams_reset(PackedScratch* s) {
     s->ev_fork = nullptr;
 }
 
-static inline void packed_scratch_free(PackedScratch* s) {
-    packed_streams_reset(s);
-    if (s->jt) (void)hipFree(s->jt);
-    if (s->sorted) (void)hipFree(s->sorted);
-    if (s->jobinfo) (void)hipFree(s->jobinfo);
-    s->jobinfo = nullptr; s->cap_jobinfo = 0;
-    if (s->bests) (void)hipFree(s->bests);
-    if (s->tilebuf) (void)hipFree(s->tilebuf);
-    if (s->tmeta) (void)hipFree(s->tmeta);
-    if (s->raws) (void)hipFree(s->raws);
-    s->raws = nullptr; s->cap_raws = 0;
-    if (s->part) (void)hipFree(s->part);
-    if (s->redo) (void)hipFree(s->redo);
-    if (s->posof) (void)hipFree(s->posof);
-    if (s->bcres) (void)hipFree(s->bcres);
-    if (s->fin) (void)hipFree(s->fin);
-    s->fin = nullptr; s->cap_fin = 0;
-    s->posof = nullptr; s->cap_posof = 0; s->bcres = nullptr; s->cap_bcres = 0;
-    if (s->abs_planes) (void)hipFree(s->abs_planes);
-    if (s->abs_valid) (void)hipFree(s->abs_valid);
-    if (s->abs_flags) (void)hipFree(s->abs_flags);
-    s->abs_planes = nullptr; s->cap_abs_planes = 0; s->abs_valid = nullptr; s->cap_abs_valid = 0; s->abs_flags = nullptr; s->cap_abs_flags = 0;
-    if (s->bsplan) (void)hipFree(s->bsplan);
-    if (s->bskeys) (void)hipFree(s->bskeys);
-    if (s->bsrp) (void)hipFree(s->bsrp);
-    s->bsplan = nullptr; s->bskeys = nullptr; s->cap_bskeys = 0; s->bsrp = nullptr; s->cap_bsrp = 0;
-    s->part = nullptr; s->cap_part = 0; s->redo = nullptr; s->cap_redo = 0;
-    s->tilebuf = nullptr; s->tmeta = nullptr; s->cap_tiles = 0;
-    s->jt = nullptr; s->sorted = nullptr; s->cap_sorted = 0; s->bests = nullptr; s->cap_bests = 0;
-}
+// (the buffers free themselves with the scratch; the streams and events go here, on the context's device)
+static inline void packed_scratch_free(PackedScratch* s) { packed_streams_reset(s); }
 
 static inline int packed_max_width(const DevKit& k) {
     int m = 0;
@@ -208,6 +175,12 @@ static inline bool packed_supported(const DevKit& k) {
 static inline int packed_fail(const char* what, hipError_t e) {
     g_packed_err = std::string(what) + ": " + hipGetErrorString(e);
     return (int)QCAT_ERR_DEVICE;
+}
+// room for n elements in a scratch buffer of the packed path, or this layer's error naming the buffer
+template <class T>
+static inline int packed_ensure(DevBuf<T>& b, size_t n, const char* what) {
+    const hipError_t e = b.ensure(n);
+    return e == hipSuccess ? 0 : packed_fail(("hipMalloc(" + std::string(what) + ")").c_str(), e);
 }
 
 // ---- bit-sliced adapter kernels: when, and their buffers ------------------------------------------------------------
@@ -260,27 +233,13 @@ static inline bool packed_abs_wanted(const DevKit& hk, uint32_t n_ends, bool hav
 // planes, keep masks and the zeroed flag block [tile cursors: MAX_T u32][tile_any: tiles u32][need128: tiles * 16 bytes]
 static inline int packed_abs_buffers(hipStream_t stream, const DevKit& hk, uint32_t n_ends, PackedScratch* sc) {
     hipError_t e;
+    int rc;
     const uint32_t abs_tiles = (n_ends + ABS_TILE - 1) / ABS_TILE;
     const size_t need_planes = (size_t)abs_tiles * hk.max_align * 64, need_valid = (size_t)abs_tiles * 64;
     const size_t need_flags = (size_t)MAX_T * 4 + (size_t)abs_tiles * 4 + (size_t)abs_tiles * (ABS_TILE / PK_TILE);
-    if (need_planes > sc->cap_abs_planes) {
-        if (sc->abs_planes) (void)hipFree(sc->abs_planes);
-        sc->abs_planes = nullptr; sc->cap_abs_planes = 0;
-        if ((e = q_malloc((void**)&sc->abs_planes, need_planes * sizeof(uint2))) != hipSuccess) return packed_fail("hipMalloc(adapter letter planes)", e);
-        sc->cap_abs_planes = need_planes;
-    }
-    if (need_valid > sc->cap_abs_valid) {
-        if (sc->abs_valid) (void)hipFree(sc->abs_valid);
-        sc->abs_valid = nullptr; sc->cap_abs_valid = 0;
-        if ((e = q_malloc((void**)&sc->abs_valid, need_valid * 4)) != hipSuccess) return packed_fail("hipMalloc(adapter keep masks)", e);
-        sc->cap_abs_valid = need_valid;
-    }
-    if (need_flags > sc->cap_abs_flags) {
-        if (sc->abs_flags) (void)hipFree(sc->abs_flags);
-        sc->abs_flags = nullptr; sc->cap_abs_flags = 0;
-        if ((e = q_malloc((void**)&sc->abs_flags, need_flags)) != hipSuccess) return packed_fail("hipMalloc(adapter tile flags)", e);
-        sc->cap_abs_flags = need_flags;
-    }
+    if ((rc = packed_ensure(sc->abs_planes, need_planes, "adapter letter planes"))) return rc;
+    if ((rc = packed_ensure(sc->abs_valid, need_valid, "adapter keep masks"))) return rc;
+    if ((rc = packed_ensure(sc->abs_flags, need_flags, "adapter tile flags"))) return rc;
     if ((e = packed_fill(sc->abs_flags, 0, need_flags, stream)) != hipSuccess) return packed_fail("memset(adapter tile flags)", e);
     sc->abs_zeroed = n_ends;
     return 0;
@@ -293,39 +252,15 @@ static inline int packed_prepare(hipStream_t stream, const DevKit& hk, uint32_t 
     const size_t n_cand = (size_t)n_ends * nsets;
     const size_t need_sorted = n_cand + (size_t)JOB_GROUPS * PK_TILE;
     hipError_t e;
-    if (!sc->jt && (e = q_malloc((void**)&sc->jt, sizeof(JobTables))) != hipSuccess) return fail("hipMalloc(job tables)", e);
+    int rc;
+    if ((rc = packed_ensure(sc->jt, 1, "job tables"))) return rc;
     if ((e = packed_streams(sc)) != hipSuccess) return fail("side streams", e);
-    if (need_sorted > sc->cap_sorted) {
-        if (sc->sorted) (void)hipFree(sc->sorted);
-        sc->sorted = nullptr; sc->cap_sorted = 0;
-        if ((e = q_malloc((void**)&sc->sorted, need_sorted * 4)) != hipSuccess) return fail("hipMalloc(sorted jobs)", e);
-        sc->cap_sorted = need_sorted;
-    }
-    if (n_cand > sc->cap_jobinfo) {
-        if (sc->jobinfo) (void)hipFree(sc->jobinfo);
-        sc->jobinfo = nullptr; sc->cap_jobinfo = 0;
-        if ((e = q_malloc((void**)&sc->jobinfo, std::max<size_t>(n_cand, 1) * 4)) != hipSuccess) return fail("hipMalloc(job words)", e);
-        sc->cap_jobinfo = n_cand;
-    }
+    if ((rc = packed_ensure(sc->sorted, need_sorted, "sorted jobs"))) return rc;
+    if ((rc = packed_ensure(sc->jobinfo, n_cand, "job words"))) return rc;
     if (sc->slim) {
-        if (n_cand > sc->cap_posof) {
-            if (sc->posof) (void)hipFree(sc->posof);
-            sc->posof = nullptr; sc->cap_posof = 0;
-            if ((e = q_malloc((void**)&sc->posof, std::max<size_t>(n_cand, 1) * 4)) != hipSuccess) return fail("hipMalloc(job positions)", e);
-            sc->cap_posof = n_cand;
-        }
-        if (n_cand > sc->cap_bcres) {
-            if (sc->bcres) (void)hipFree(sc->bcres);
-            sc->bcres = nullptr; sc->cap_bcres = 0;
-            if ((e = q_malloc((void**)&sc->bcres, std::max<size_t>(n_cand, 1) * sizeof(int2))) != hipSuccess) return fail("hipMalloc(barcode results)", e);
-            sc->cap_bcres = n_cand;
-        }
-        if (n_ends > sc->cap_fin) {
-            if (sc->fin) (void)hipFree(sc->fin);
-            sc->fin = nullptr; sc->cap_fin = 0;
-            if ((e = q_malloc((void**)&sc->fin, std::max<size_t>(n_ends, 1) * 4)) != hipSuccess) return fail("hipMalloc(finalize words)", e);
-            sc->cap_fin = n_ends;
-        }
+        if ((rc = packed_ensure(sc->posof, n_cand, "job positions"))) return rc;
+        if ((rc = packed_ensure(sc->bcres, n_cand, "barcode results"))) return rc;
+        if ((rc = packed_ensure(sc->fin, n_ends, "finalize words"))) return rc;
     }
     if ((e = packed_fill(sc->jt, 0, sizeof(JobTables), stream)) != hipSuccess) return fail("memset(job tables)", e);
     if ((e = packed_fill(sc->sorted, 0xFF, need_sorted * 4, stream)) != hipSuccess) return fail("memset(sorted)", e);
@@ -361,6 +296,7 @@ static inline int packed_adapter(hipStream_t stream, KitPtrs kp, const DevKit& h
                                  int32_t* dbg_tpl, Mark mark) {
     auto fail = packed_fail;
     hipError_t e;
+    int rc;
     // (launches of different width classes are independent; running them on two streams was
     //  measured and gave no overlap benefit on MI355X, so everything stays on the context's stream)
     const int adapter_widths[] = {40, 48, 56, 60, 64, 84, 92, 104, 112, 120, 128};
@@ -371,12 +307,7 @@ static inline int packed_adapter(hipStream_t stream, KitPtrs kp, const DevKit& h
     int n_slices = 0, n_static_a = 0;
     for (int w : adapter_widths) { bool present = false; for (int t = 0; t < hk.nt; ++t) present |= table_tpl(t, w); n_slices += present; }
     for (int t = 0; t < hk.nt; ++t) if (use_static_a && hk.tpl[t].static_kernel >= 0) { ++n_slices; ++n_static_a; }
-    if ((size_t)n_ends * n_slices > sc->cap_bests) {
-        if (sc->bests) (void)hipFree(sc->bests);
-        sc->bests = nullptr; sc->cap_bests = 0;
-        if ((e = q_malloc((void**)&sc->bests, (size_t)n_ends * n_slices * sizeof(AdapterBest))) != hipSuccess) return fail("hipMalloc(adapter bests)", e);
-        sc->cap_bests = (size_t)n_ends * n_slices;
-    }
+    if ((rc = packed_ensure(sc->bests, (size_t)n_ends * n_slices, "adapter bests"))) return rc;
     const uint32_t tiles = (n_ends + PK_TILE - 1) / PK_TILE;
     const uint32_t blocks = (tiles + PK_WAVES - 1) / PK_WAVES;
     {
@@ -432,7 +363,7 @@ static inline int packed_adapter(hipStream_t stream, KitPtrs kp, const DevKit& h
             const bool ready = sc->abs_ready == n_ends;
             if (!ready && sc->abs_zeroed != n_ends) { const int rc2 = packed_abs_buffers(stream, hk, n_ends, sc); if (rc2) return rc2; }
             sc->abs_zeroed = 0;
-            abs_cursor = reinterpret_cast<uint32_t*>(sc->abs_flags);
+            abs_cursor = reinterpret_cast<uint32_t*>(sc->abs_flags.get());
             abs_tile_any = abs_cursor + MAX_T;
             abs_need128 = reinterpret_cast<uint8_t*>(abs_tile_any + abs_tiles);
             if (!ready)
@@ -498,7 +429,7 @@ static inline int packed_adapter(hipStream_t stream, KitPtrs kp, const DevKit& h
     sc->n_slices = n_slices;
     sc->slices_single = n_static_a == n_slices;       // every slice holds exactly one template (static-letter kernels)
     if ((e = hipGetLastError()) != hipSuccess) return fail("packed kernel launch", e);
-    int rc = jit_take_error();
+    rc = jit_take_error();
     if (rc) return rc;
     return packed_adapter_finish(stream, kp, win, wlen, n_ends, recs, sc, -1);
 }
@@ -510,6 +441,7 @@ static inline int packed_barcode(hipStream_t stream, KitPtrs kp, const DevKit& h
                                  PackedScratch* sc, Gather gather, int16_t* dbg_rows, uint32_t stride, Mark mark) {
     auto fail = packed_fail;
     hipError_t e;
+    int rc;
     const int nsets = hk.mode == QCAT_MODE_DUAL ? 2 : 1;
     const size_t n_cand = (size_t)n_ends * nsets;
     const size_t need_sorted = n_cand + (size_t)JOB_GROUPS * PK_TILE;
@@ -520,14 +452,8 @@ static inline int packed_barcode(hipStream_t stream, KitPtrs kp, const DevKit& h
         hipLaunchKernelGGL(k_job_scatter, dim3(sblocks), dim3(256), 0, stream, sc->jobinfo, n_ends, nsets, sc->jt, sc->sorted, sc->slim ? sc->posof : nullptr);
     }
     const uint32_t max_tiles = (uint32_t)(need_sorted / PK_TILE);
-    if (max_tiles > sc->cap_tiles) {
-        if (sc->tilebuf) (void)hipFree(sc->tilebuf);
-        if (sc->tmeta) (void)hipFree(sc->tmeta);
-        sc->tilebuf = nullptr; sc->tmeta = nullptr; sc->cap_tiles = 0;
-        if ((e = q_malloc((void**)&sc->tilebuf, (size_t)max_tiles * 64 * WIN_STRIDE)) != hipSuccess) return fail("hipMalloc(tile images)", e);
-        if ((e = q_malloc((void**)&sc->tmeta, (size_t)max_tiles * 64 * sizeof(TileMeta))) != hipSuccess) return fail("hipMalloc(tile meta)", e);
-        sc->cap_tiles = max_tiles;
-    }
+    if ((rc = packed_ensure(sc->tilebuf, (size_t)max_tiles * 64 * WIN_STRIDE, "tile images"))) return rc;
+    if ((rc = packed_ensure(sc->tmeta, (size_t)max_tiles * 64, "tile meta"))) return rc;
     // the tile images are made right before their first reader: the bit-sliced kernels read the hot regions from the
     // windows themselves, and k_bs_plan (which says what they take) has to run before the gather that leaves those tiles out
     bool gathered = false;
@@ -583,12 +509,7 @@ static inline int packed_barcode(hipStream_t stream, KitPtrs kp, const DevKit& h
         for (int t = 0; t < hk.nt && summary; ++t)
             for (int s = 0; s < nsets; ++s) if (hk.tpl[t].sets[s].static_kernel < 0) { summary = false; break; }
         const size_t need_raws = summary ? 0 : (size_t)max_tiles * bstride * 64;
-        if (need_raws > sc->cap_raws) {
-            if (sc->raws) (void)hipFree(sc->raws);
-            sc->raws = nullptr; sc->cap_raws = 0;
-            if ((e = q_malloc((void**)&sc->raws, need_raws * 4)) != hipSuccess) return fail("hipMalloc(raw barcode scores)", e);
-            sc->cap_raws = need_raws;
-        }
+        if (need_raws && (rc = packed_ensure(sc->raws, need_raws, "raw barcode scores"))) return rc;
         // barcodes per work unit: ~4 (a unit of 4 x 47 rows still amortises its staging to < 2 %)
         const QOptVal chunk_env = qopt_get(QO_CHUNK_BARCODES);
         const int chunk_b = chunk_env ? std::max(1, atoi(chunk_env)) : 4;
@@ -646,19 +567,9 @@ static inline int packed_barcode(hipStream_t stream, KitPtrs kp, const DevKit& h
             }
             if (summary) {
                 const size_t need_part = (size_t)max_tiles * part_stride * 128, need_redo = (size_t)max_tiles * 128 + 1;
-                if (need_part > sc->cap_part) {
-                    if (sc->part) (void)hipFree(sc->part);
-                    sc->part = nullptr; sc->cap_part = 0;
-                    if ((e = q_malloc((void**)&sc->part, need_part * 4)) != hipSuccess) return fail("hipMalloc(barcode keys)", e);
-                    sc->cap_part = need_part;
-                }
-                if (need_redo > sc->cap_redo) {
-                    if (sc->redo) (void)hipFree(sc->redo);
-                    sc->redo = nullptr; sc->cap_redo = 0;
-                    if ((e = q_malloc((void**)&sc->redo, need_redo * 4)) != hipSuccess) return fail("hipMalloc(redo list)", e);
-                    sc->cap_redo = need_redo;
-                    sc->redo_zeroed = false;                 // (packed_prepare zeroed the count of the buffer that was just freed)
-                }
+                if ((rc = packed_ensure(sc->part, need_part, "barcode keys"))) return rc;
+                if (need_redo > sc->redo.cap()) sc->redo_zeroed = false;                 // (packed_prepare zeroed the count of a buffer that is freed now)
+                if ((rc = packed_ensure(sc->redo, need_redo, "redo list"))) return rc;
                 if (!sc->redo_zeroed && (e = hipMemsetAsync(sc->redo, 0, 4, stream)) != hipSuccess) return fail("memset(redo count)", e);
                 sc->redo_zeroed = false;
             }
@@ -707,22 +618,12 @@ static inline int packed_barcode(hipStream_t stream, KitPtrs kp, const DevKit& h
                 }
                 if (any) {
                     const size_t need_keys = (size_t)BS_MAX_CHUNKS * need_sorted;
-                    if (!sc->bsplan && (e = q_malloc((void**)&sc->bsplan, sizeof(BsPlan))) != hipSuccess) return fail("hipMalloc(bit-slice plan)", e);
-                    if (need_keys > sc->cap_bskeys) {
-                        if (sc->bskeys) (void)hipFree(sc->bskeys);
-                        sc->bskeys = nullptr; sc->cap_bskeys = 0;
-                        if ((e = q_malloc((void**)&sc->bskeys, need_keys * 4)) != hipSuccess) return fail("hipMalloc(bit-slice keys)", e);
-                        sc->cap_bskeys = need_keys;
-                    }
+                    if ((rc = packed_ensure(sc->bsplan, 1, "bit-slice plan"))) return rc;
+                    if ((rc = packed_ensure(sc->bskeys, need_keys, "bit-slice keys"))) return rc;
                     // a workgroup's unit parks the trailing columns' plane pairs in global memory (8 bytes per row and lane: 77 KB per
                     // workgroup, read back from L2 by its own waves; one workgroup per CU and launch)
                     const size_t need_rp = (size_t)n_owns * (size_t)cus * BS_MAX_ROWS * 64;
-                    if (need_rp > sc->cap_bsrp) {
-                        if (sc->bsrp) (void)hipFree(sc->bsrp);
-                        sc->bsrp = nullptr; sc->cap_bsrp = 0;
-                        if ((e = q_malloc((void**)&sc->bsrp, need_rp * sizeof(uint2))) != hipSuccess) return fail("hipMalloc(bit-slice trailing planes)", e);
-                        sc->cap_bsrp = need_rp;
-                    }
+                    if ((rc = packed_ensure(sc->bsrp, need_rp, "bit-slice trailing planes"))) return rc;
                     hipLaunchKernelGGL(k_bs_plan, dim3(1), dim3(256), 0, stream, kp.kit, sc->jt, bsn, sc->bsplan,
                                        opt_on(QO_BS_NO_TAIL_SPLIT) ? 0 : cus, bs_pad_min, (bs_direct && !opt_on(QO_BS_NO_SHORT)) ? 1 : 0);
                     // (Round 4, measured and dropped: the tile images of a medium batch made on a side stream beside the bit-sliced
@@ -735,9 +636,9 @@ static inline int packed_barcode(hipStream_t stream, KitPtrs kp, const DevKit& h
                     // config 3 -0.2 ms, shipped dual kit -0.05 ms; before, big batches kept them in line: max_super < 4 CUs' worth)
                     leftover_beside = lo_env ? atoi(lo_env) != 0 : true;
                     ensure_gather(bs_direct ? sc->bsplan : nullptr);
-                    unsigned long long* bs_trace = nullptr;
+                    DevBuf<unsigned long long> bs_trace;
                     const size_t bs_trace_words = (size_t)BS_TRACE_STAMPS + 1 + (size_t)BS_TRACE_LOG * 4;
-                    if (opt_on(QO_BS_TRACE)) { (void)hipMalloc((void**)&bs_trace, bs_trace_words * 8); (void)hipMemsetAsync(bs_trace, 0, bs_trace_words * 8, stream); }
+                    if (opt_on(QO_BS_TRACE) && bs_trace.ensure(bs_trace_words) == hipSuccess) (void)hipMemsetAsync(bs_trace, 0, bs_trace_words * 8, stream);
                     // big batches: the launches (one per target family) go to side streams.  A workgroup holds a whole
                     // CU, so they cannot share one, but the next launch's workgroups take the CUs the previous one's
                     // tail frees (its last units end up to a unit -- 0.3 to 1 ms -- apart): config 3 238.3 -> 239.6 M
@@ -771,7 +672,6 @@ static inline int packed_barcode(hipStream_t stream, KitPtrs kp, const DevKit& h
                         std::vector<unsigned long long> ht(bs_trace_words);
                         (void)hipStreamSynchronize(stream);
                         (void)hipMemcpy(ht.data(), bs_trace, ht.size() * 8, hipMemcpyDeviceToHost);
-                        (void)hipFree(bs_trace);
                         for (int q = 0; q < n_owns; ++q)
                             for (int u = 0; u < 8; ++u) {
                                 const unsigned long long t0 = ht[((size_t)q * 8 + u) * BS_WAVES * 8];

@@ -472,20 +472,19 @@ constexpr int MAX_TIMED = 12;
 struct qcat_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    // per-scan buffers (grown on demand)
-    size_t cap_win = 0, cap_wlen = 0, cap_recs = 0, cap_reads = 0, cap_buckets = 0;
-    uint8_t* win = nullptr;
-    int32_t* wlen = nullptr;
-    uint8_t* wspec = nullptr; size_t cap_wspec = 0;     // per read end: the window holds a letter outside A, C, G, T, N
-    uint32_t* win2 = nullptr; size_t cap_win2 = 0;      // the windows at two bits per code (plain windows: the bit-sliced kernels' input)
+    // per-scan buffers (grown on demand; every buffer owns its memory and knows its capacity: dev_buf.h)
+    DevBuf<uint8_t> win;
+    DevBuf<int32_t> wlen;
+    DevBuf<uint8_t> wspec;                              // per read end: the window holds a letter outside A, C, G, T, N
+    DevBuf<uint32_t> win2;                              // the windows at two bits per code (plain windows: the bit-sliced kernels' input)
     bool win2_valid = false;                            // ... written by the pack kernel of the windows in `win`
-    EndRec* recs = nullptr;
-    qcat_result* results = nullptr;
-    unsigned long long* counts = nullptr;
+    DevBuf<EndRec> recs;
+    DevBuf<qcat_result> results;
+    DevBuf<unsigned long long> counts;
     // pinned staging of window-only uploads (qcat_scan_batch): compact bases, offsets, real lengths
-    uint8_t* pin_bases = nullptr; size_t cap_pin_bases = 0;
-    uint64_t* pin_offsets = nullptr; uint32_t* pin_len = nullptr; size_t cap_pin_reads = 0;
-    uint8_t* pin_ret = nullptr; size_t cap_pin_ret = 0;     // what a host-buffer call brings back (records, votes, counts): copies into PINNED
+    PinBuf<uint8_t> pin_bases;
+    PinBuf<uint64_t> pin_offsets; PinBuf<uint32_t> pin_len;
+    PinBuf<uint8_t> pin_ret;                                // what a host-buffer call brings back (records, votes, counts): copies into PINNED
                                                             // memory are one DMA each; into the caller's pageable arrays the runtime stages
                                                             // every one through a copy kernel and a host memcpy (round 6: five of them were
                                                             // 100 us of a 4000-read kit-auto call)
@@ -493,22 +492,21 @@ struct qcat_ctx {
     std::vector<qcat_ctx*> helpers;                // contexts of the kit-auto file loop's other workers (fastq_host.inc), created on first use
     PackedScratch packed;
     // packed --detect-middle (kernels_middle.inc): M-end sort tables and per-slot arrays
-    MidTables* mid_tables = nullptr;
-    uint8_t* mid_generic = nullptr; size_t cap_mid_generic = 0;
-    uint32_t* mid_slot = nullptr; size_t cap_mid_slot = 0;
-    uint32_t* mid_sorted = nullptr; int32_t* mid_len = nullptr; int32_t* mid_fallback = nullptr;
-    uint32_t* mid_win2 = nullptr; uint8_t* mid_wspec = nullptr;   // the M-ends' first window at two bits per code + flags (k_mid_windows)
-    EndRec* mid_recs = nullptr; AdapterBest* mid_bests = nullptr;
-    size_t cap_mid_slots = 0, cap_mid_bests = 0;
+    DevBuf<MidTables> mid_tables;                                 // (allocated once)
+    DevBuf<uint8_t> mid_generic;
+    DevBuf<uint32_t> mid_slot;
+    DevBuf<uint32_t> mid_sorted; DevBuf<int32_t> mid_len, mid_fallback;
+    DevBuf<uint32_t> mid_win2; DevBuf<uint8_t> mid_wspec;         // the M-ends' first window at two bits per code + flags (k_mid_windows)
+    DevBuf<EndRec> mid_recs; DevBuf<AdapterBest> mid_bests;
     // ... its bit-sliced adapter scan (kernels_abs_mid.inc): per big tile of 2048 slots [rows, padding zone, kit, first row: 4 x tiles]
     // [nonempty, invalid: 2 x 64 x tiles] [cursors: MAX_T], the per-128 flags, letter planes and not-started masks
-    uint32_t* absm_tiles = nullptr; size_t cap_absm_tiles = 0;
-    uint8_t* absm_need = nullptr; size_t cap_absm_need = 0;
-    uint2* absm_planes = nullptr; size_t cap_absm_planes = 0;
-    uint32_t* absm_ns = nullptr; size_t cap_absm_ns = 0;
-    uint32_t* absm_c2 = nullptr; size_t cap_absm_c2 = 0;          // the batch at two bits per base (with ABSM_C2_SLACK dwords on either side)
-    uint8_t* absm_rspec = nullptr; size_t cap_absm_rspec = 0;
-    uint4* absm_sinfo = nullptr; size_t cap_absm_sinfo = 0;      // per slot: position / strand, length, special flag
+    DevBuf<uint32_t> absm_tiles;
+    DevBuf<uint8_t> absm_need;
+    DevBuf<uint2> absm_planes;
+    DevBuf<uint32_t> absm_ns;
+    DevBuf<uint32_t> absm_c2;                                     // the batch at two bits per base (with ABSM_C2_SLACK dwords on either side)
+    DevBuf<uint8_t> absm_rspec;
+    DevBuf<uint4> absm_sinfo;                                     // per slot: position / strand, length, special flag
     hipStream_t absm_stream = nullptr; hipEvent_t absm_go = nullptr, absm_done = nullptr;      // the packed batch beside the read ends' kernels
     bool absm_codes_early = false;                                // this scan's k_absmid_codes is in flight on absm_stream
     uint32_t absm_last_big = 0, absm_last_128 = 0;                // big tiles / tiles of 128 slots of the latest scan on that path (0: not taken)
@@ -516,10 +514,9 @@ struct qcat_ctx {
     int last_buckets = 0;
     // device staging of the host-buffer calls (qcat_scan_batch / _auto / _debug, qcat_detect_kit): grown on demand and
     // reused -- a 4000-read batch of the reference driver's call shape spent a third of its call in six hipMalloc / hipFree
-    uint8_t* hb_bases = nullptr; size_t cap_hb_bases = 0;
-    uint64_t* hb_offsets = nullptr; uint32_t* hb_len = nullptr; size_t cap_hb_reads = 0;
-    unsigned long long* vote_buf = nullptr;        // per batch of a kit vote: MAX_T counters, MAX_T first voters, then one chosen slot each
-    size_t cap_vote_batches = 0;
+    DevBuf<uint8_t> hb_bases;
+    DevBuf<uint64_t> hb_offsets; DevBuf<uint32_t> hb_len;
+    DevBuf<uint8_t> vote_buf;                      // per batch of a kit vote: MAX_T counters, MAX_T first voters, then one chosen slot each (+ 16 bytes)
     // the device work of a kit-auto host-buffer call as a captured graph (scan_batch_auto_impl): two dozen launches (round 5: ~45 on
     // twelve streams) replayed by one hipGraphLaunch when a call has the shape of the one before it
     struct ApiGraph {
@@ -530,21 +527,21 @@ struct qcat_ctx {
         uint64_t replays = 0;
     } api_graph, scan_graph;                       // kit-auto calls (scan_batch_auto_impl); calls with a named kit (qcat_scan_batch, round 5)
     // the handful-of-reads path (kernels_tiny.inc): per read end the templates' (raw, end) and the barcodes' raw scores
-    int32_t* tiny_tpl = nullptr; int16_t* tiny_sc = nullptr; size_t cap_tiny = 0, cap_tiny_ends = 0;
+    DevBuf<int32_t> tiny_tpl; DevBuf<int16_t> tiny_sc;
     uint32_t last_tiny_ends = 0;                   // read ends the last scan put on that path (0: another path)
     uint32_t last_fused_ends = 0;                  // read ends whose windows and letter planes the last scan made in one kernel (k_pack_planes)
-    int32_t* tiny_simple = nullptr; size_t cap_tiny_simple = 0;    // simple kits on qcat_scan_sequences: (raw, end_query) per (sequence, barcode) of a piece
+    DevBuf<int32_t> tiny_simple;                   // simple kits on qcat_scan_sequences: (raw, end_query) per (sequence, barcode) of a piece
     // simple mode on the packed kernels (kernels_simple.inc): one (key, end) per (work unit, read end); the read ends whose best raw
     // score is 0 ([0]: their count); debug scans with rows: (raw, end) of every barcode
-    uint2* simple_part = nullptr; size_t cap_simple_part = 0;
-    uint32_t* simple_redo = nullptr; size_t cap_simple_redo = 0;
-    uint32_t* simple_full = nullptr; size_t cap_simple_full = 0;
+    DevBuf<uint2> simple_part;
+    DevBuf<uint32_t> simple_redo;
+    DevBuf<uint32_t> simple_full;
     // --detect-middle: the reads the packed interior scan leaves (long interiors) on the same kernels (k_midw_*)
-    uint32_t* midw_list = nullptr; int32_t* midw_tpl = nullptr; EndRec* midw_recs = nullptr; int16_t* midw_sc = nullptr; size_t cap_midw_sc = 0;
+    DevBuf<uint32_t> midw_list; DevBuf<int32_t> midw_tpl; DevBuf<EndRec> midw_recs; DevBuf<int16_t> midw_sc;    // (the first three: allocated once)
     bool midw_ran = false;
     // debug buffers
-    int32_t* dbg_tpl = nullptr; size_t cap_dbg_tpl = 0;
-    int16_t* dbg_rows = nullptr; size_t cap_dbg_rows = 0;
+    DevBuf<int32_t> dbg_tpl;
+    DevBuf<int16_t> dbg_rows;
     // timing: a ring of event sets, one per scan, so that timed scans need no host synchronisation
     // between them; qcat_ctx_last_timing drains the ring
     bool timing = false;
@@ -583,28 +580,14 @@ extern "C" void qcat_ctx_destroy(qcat_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->api_graph.exec) (void)hipGraphExecDestroy(c->api_graph.exec);
     if (c->scan_graph.exec) (void)hipGraphExecDestroy(c->scan_graph.exec);
-    (void)hipFree(c->win); (void)hipFree(c->wlen); (void)hipFree(c->wspec); (void)hipFree(c->win2); (void)hipFree(c->recs); (void)hipFree(c->results);
-    (void)hipFree(c->counts); (void)hipFree(c->dbg_tpl); (void)hipFree(c->dbg_rows); (void)hipFree(c->tiny_tpl); (void)hipFree(c->tiny_sc); (void)hipFree(c->tiny_simple);
-    (void)hipFree(c->simple_part); (void)hipFree(c->simple_redo); (void)hipFree(c->simple_full);
-    (void)hipFree(c->midw_list); (void)hipFree(c->midw_tpl); (void)hipFree(c->midw_recs); (void)hipFree(c->midw_sc);
-    (void)hipFree(c->hb_bases); (void)hipFree(c->hb_offsets); (void)hipFree(c->hb_len); (void)hipFree(c->vote_buf);
     packed_scratch_free(&c->packed);
-    if (c->pin_bases) (void)hipHostFree(c->pin_bases);
-    if (c->pin_offsets) (void)hipHostFree(c->pin_offsets);
-    if (c->pin_len) (void)hipHostFree(c->pin_len);
-    if (c->pin_ret) (void)hipHostFree(c->pin_ret);
     pipeline_free(c->pipe);
-    (void)hipFree(c->mid_tables); (void)hipFree(c->mid_generic); (void)hipFree(c->mid_slot); (void)hipFree(c->mid_sorted);
-    (void)hipFree(c->mid_len); (void)hipFree(c->mid_fallback); (void)hipFree(c->mid_recs); (void)hipFree(c->mid_bests);
-    (void)hipFree(c->mid_win2); (void)hipFree(c->mid_wspec);
-    (void)hipFree(c->absm_tiles); (void)hipFree(c->absm_need); (void)hipFree(c->absm_planes); (void)hipFree(c->absm_ns);
-    (void)hipFree(c->absm_c2); (void)hipFree(c->absm_rspec); (void)hipFree(c->absm_sinfo);
     if (c->absm_stream) (void)hipStreamDestroy(c->absm_stream);
     if (c->absm_go) (void)hipEventDestroy(c->absm_go);
     if (c->absm_done) (void)hipEventDestroy(c->absm_done);
     if (c->ev_ready) for (int r = 0; r < qcat_ctx::TIME_RING; ++r) for (int i = 0; i <= MAX_TIMED; ++i) (void)hipEventDestroy(c->evr[r][i]);
     (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                      // (every scratch buffer frees itself: dev_buf.h)
 }
 
 extern "C" int qcat_ctx_set_timing(qcat_ctx* c, int enabled) {
@@ -619,15 +602,11 @@ extern "C" int qcat_ctx_set_timing(qcat_ctx* c, int enabled) {
     return 0;
 }
 
+// room for `need` elements in a scratch buffer of the context, or this layer's out-of-memory error
 template <class T>
-static int grow(T** p, size_t* cap, size_t need) {
-    if (need <= *cap && *p) return 0;
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    size_t n = std::max<size_t>(need, 1);
-    hipError_t e = q_malloc((void**)p, n * sizeof(T));
-    if (e != hipSuccess) { *cap = 0; return set_err(QCAT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-    *cap = n;
-    return 0;
+static int grow(DevBuf<T>& buf, size_t need) {
+    const hipError_t e = buf.ensure(need);
+    return e == hipSuccess ? 0 : set_err(QCAT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
 }
 
 static void mark(qcat_ctx* c, const char* name) {
@@ -693,8 +672,8 @@ static int absmid_codes_early(qcat_ctx* c, const DevKit& hk, const qcat_batch* b
         HIPCHK(hipEventCreateWithFlags(&c->absm_go, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&c->absm_done, hipEventDisableTiming));
     }
-    if ((rc = grow(&c->absm_c2, &c->cap_absm_c2, (size_t)(b->n_bases / 16) + 4 + 2 * ABSM_C2_SLACK_HOST))) return rc;
-    if ((rc = grow(&c->absm_rspec, &c->cap_absm_rspec, (size_t)n + 1))) return rc;
+    if ((rc = grow(c->absm_c2, (size_t)(b->n_bases / 16) + 4 + 2 * ABSM_C2_SLACK_HOST))) return rc;
+    if ((rc = grow(c->absm_rspec, (size_t)n + 1))) return rc;
     AbsMidArgs am{};
     am.bases = b->bases; am.offsets = b->offsets; am.max_align = hk.max_align; am.n_bases = b->n_bases; am.n_reads = n;
     am.c2 = c->absm_c2 + ABSM_C2_SLACK_HOST; am.rspec = c->absm_rspec;
@@ -714,33 +693,28 @@ static int middle_packed(qcat_ctx* c, KitPtrs kp, const DevKit& hk, const qcat_b
     int rc;
     const size_t slots = middle_slots(hk, n);
     if (slots >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "batch too large for the packed interior scan");
-    if (!c->mid_tables) HIPCHK(hipMalloc((void**)&c->mid_tables, sizeof(MidTables)));
-    if ((rc = grow(&c->mid_generic, &c->cap_mid_generic, (size_t)n))) return rc;
-    if ((rc = grow(&c->mid_slot, &c->cap_mid_slot, (size_t)n))) return rc;
-    if (slots > c->cap_mid_slots) {
-        (void)hipFree(c->mid_sorted); (void)hipFree(c->mid_len); (void)hipFree(c->mid_fallback); (void)hipFree(c->mid_recs);
-        (void)hipFree(c->mid_win2); (void)hipFree(c->mid_wspec);
-        c->mid_sorted = nullptr; c->mid_len = nullptr; c->mid_fallback = nullptr; c->mid_recs = nullptr; c->cap_mid_slots = 0;
-        c->mid_win2 = nullptr; c->mid_wspec = nullptr;
-        HIPCHK(hipMalloc((void**)&c->mid_win2, (slots * WIN2_WORDS + 64) * 4));
-        HIPCHK(hipMalloc((void**)&c->mid_wspec, slots + 4));
-        HIPCHK(hipMalloc((void**)&c->mid_sorted, slots * 4));
-        HIPCHK(hipMalloc((void**)&c->mid_len, slots * 4));
-        HIPCHK(hipMalloc((void**)&c->mid_fallback, slots * 4));
-        HIPCHK(hipMalloc((void**)&c->mid_recs, slots * sizeof(EndRec)));
-        c->cap_mid_slots = slots;
-    }
-    if ((rc = grow(&c->mid_bests, &c->cap_mid_bests, slots * (size_t)hk.nt))) return rc;
+    HIPCHK(c->mid_tables.ensure(1));
+    if ((rc = grow(c->mid_generic, (size_t)n))) return rc;
+    if ((rc = grow(c->mid_slot, (size_t)n))) return rc;
+    HIPCHK(c->mid_win2.ensure(slots * WIN2_WORDS + 64));
+    HIPCHK(c->mid_wspec.ensure(slots + 4));
+    HIPCHK(c->mid_sorted.ensure(slots));
+    HIPCHK(c->mid_len.ensure(slots));
+    HIPCHK(c->mid_fallback.ensure(slots));
+    HIPCHK(c->mid_recs.ensure(slots));
+    if ((rc = grow(c->mid_bests, slots * (size_t)hk.nt))) return rc;
     // the fills of the interior scan leave as two k_fill_multi launches (round 5; thirteen memsets of 5-7 us each before):
     // the slot tables here, the job tables / sorted list / redo count / letter flags / tile cursors before the adapter phase
     const bool merge_fills = !opt_on(QO_NO_FILL_MERGE);
-    g_fill.n = 0; g_fill_defer = merge_fills;
-    HIPCHK(packed_fill(c->mid_tables, 0, sizeof(MidTables), st));
-    HIPCHK(packed_fill(c->mid_slot, 0xFF, (size_t)n * 4, st));
-    HIPCHK(packed_fill(c->mid_sorted, 0xFF, slots * 4, st));
-    HIPCHK(packed_fill(c->mid_len, 0, slots * 4, st));
-    HIPCHK(packed_fill(c->mid_fallback, 0, slots * 4, st));
-    HIPCHK(packed_fill_flush(st));
+    {
+        FillScope fills(merge_fills);
+        HIPCHK(packed_fill(c->mid_tables, 0, sizeof(MidTables), st));
+        HIPCHK(packed_fill(c->mid_slot, 0xFF, (size_t)n * 4, st));
+        HIPCHK(packed_fill(c->mid_sorted, 0xFF, slots * 4, st));
+        HIPCHK(packed_fill(c->mid_len, 0, slots * 4, st));
+        HIPCHK(packed_fill(c->mid_fallback, 0, slots * 4, st));
+        HIPCHK(packed_fill_flush(st));
+    }
     const uint32_t rblocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + 255) / 256, 2048);
     hipLaunchKernelGGL(k_mid_count, dim3(rblocks), dim3(256), 0, st, kp.kit, b->offsets, n, c->results, c->mid_tables, c->mid_generic);
     hipLaunchKernelGGL(k_mid_offsets, dim3(1), dim3(1024), 0, st, c->mid_tables);
@@ -765,8 +739,7 @@ static int middle_packed(qcat_ctx* c, KitPtrs kp, const DevKit& hk, const qcat_b
     sc->win = c->win;                                     // (never read: the job regions come from win2, `lazy`)
     sc->lazy = mid_bs;
     sc->slim = false;                                     // ... and the barcode results stay in the interior's own records
-    g_fill.n = 0; g_fill_defer = merge_fills;                  // (flushed in front of the adapter phase below; every return before drops the list)
-    struct FillGuard { ~FillGuard() { g_fill_defer = false; g_fill.n = 0; } } fill_guard;
+    FillScope fills(merge_fills);                          // (flushed in front of the adapter phase below; every return before drops the list)
     if ((rc = packed_prepare(st, hk, (uint32_t)slots, sc))) return set_err(rc, packed_last_error());
     const uint32_t tiles = (uint32_t)(slots / PK_TILE);
     // round 4: the adapter scan of the interiors in bit-sliced form (kernels_abs_mid.inc) from QCAT_HIP_MIDDLE_ABS_MIN slots
@@ -784,7 +757,7 @@ static int middle_packed(qcat_ctx* c, KitPtrs kp, const DevKit& hk, const qcat_b
             const QOptVal rcap = qopt_get(QO_MIDDLE_ABS_ROWS);         // (tests: a plane buffer that is too small)
             size_t rows = rcap ? (size_t)atoll(rcap)
                                : std::min<size_t>((size_t)1 << 30, (size_t)(2 * b->n_bases / 2048) * 5 / 4 + (size_t)big * 128 + 16384 + 64);
-            if (!rcap && rows * 64 > c->cap_absm_planes) {
+            if (!rcap && rows * 64 > c->absm_planes.cap()) {
                 // planes + not-started masks are 768 bytes per row (~0.9 bytes per base of the batch): never more than a quarter
                 // of the device memory that is free right now -- the big tiles beyond the room fall back to the binary16 kernel
                 // per tile (k_absmid_scan: row_cap), which needs none of it
@@ -792,18 +765,18 @@ static int middle_packed(qcat_ctx* c, KitPtrs kp, const DevKit& hk, const qcat_b
                 if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) rows = std::min(rows, std::max<size_t>(16384, free_b / 4 / 768));
             }
             const size_t tw = (size_t)big * (4 + 128) + MAX_T;
-            if ((rc = grow(&c->absm_tiles, &c->cap_absm_tiles, tw))) return rc;
-            if ((rc = grow(&c->absm_need, &c->cap_absm_need, (size_t)tiles + 16))) return rc;
-            if ((rc = grow(&c->absm_planes, &c->cap_absm_planes, rows * 64))) return rc;
-            if ((rc = grow(&c->absm_ns, &c->cap_absm_ns, rows * 64))) return rc;
+            if ((rc = grow(c->absm_tiles, tw))) return rc;
+            if ((rc = grow(c->absm_need, (size_t)tiles + 16))) return rc;
+            if ((rc = grow(c->absm_planes, rows * 64))) return rc;
+            if ((rc = grow(c->absm_ns, rows * 64))) return rc;
             constexpr size_t C2_SLACK = ABSM_C2_SLACK_HOST;
             const bool early = c->absm_codes_early;                             // (absmid_codes_early: the packed batch is on its way)
             c->absm_codes_early = false;
             if (!early) {
-                if ((rc = grow(&c->absm_c2, &c->cap_absm_c2, (size_t)(b->n_bases / 16) + 4 + 2 * C2_SLACK))) return rc;
-                if ((rc = grow(&c->absm_rspec, &c->cap_absm_rspec, (size_t)n + 1))) return rc;
+                if ((rc = grow(c->absm_c2, (size_t)(b->n_bases / 16) + 4 + 2 * C2_SLACK))) return rc;
+                if ((rc = grow(c->absm_rspec, (size_t)n + 1))) return rc;
             }
-            if ((rc = grow(&c->absm_sinfo, &c->cap_absm_sinfo, slots))) return rc;
+            if ((rc = grow(c->absm_sinfo, slots))) return rc;
             uint32_t* w = c->absm_tiles;
             am.bases = b->bases; am.offsets = b->offsets; am.msorted = c->mid_sorted; am.mlen = c->mid_len; am.mt = c->mid_tables;
             am.max_align = hk.max_align; am.n_tiles = big; am.slot_cap = (uint32_t)slots; am.nt = hk.nt; am.kit_mask = kmask;
@@ -878,16 +851,17 @@ static int middle_packed(qcat_ctx* c, KitPtrs kp, const DevKit& hk, const qcat_b
     return 0;
 }
 
+// barcodes of the kit's largest set (at least 1): the stride of the one-wave kernels' score arrays
+static int max_set_barcodes(const DevKit& hk) {
+    int maxb = 1;
+    for (int t = 0; t < hk.nt; ++t) for (int s = 0; s < 2; ++s) maxb = std::max(maxb, (int)hk.tpl[t].sets[s].n);
+    return maxb;
+}
+
 // scratch of the one-wave-per-alignment kernels (kernels_tiny.inc) for `n_ends` queries of a kit whose largest set has `maxb` barcodes
 static int tiny_buffers(qcat_ctx* c, size_t n_ends, int maxb) {
-    const size_t need = n_ends * 2 * (size_t)maxb;
-    if (need > c->cap_tiny || n_ends > c->cap_tiny_ends || !c->tiny_tpl) {
-        (void)hipFree(c->tiny_tpl); (void)hipFree(c->tiny_sc); c->tiny_tpl = nullptr; c->tiny_sc = nullptr; c->cap_tiny = 0; c->cap_tiny_ends = 0;
-        const size_t cap = std::max<size_t>(need, (size_t)TINY_MAX_WAVES * 2), cap_ends = std::max<size_t>(n_ends, 4096);
-        HIPCHK(q_malloc((void**)&c->tiny_sc, cap * sizeof(int16_t)));
-        HIPCHK(q_malloc((void**)&c->tiny_tpl, cap_ends * MAX_T * 2 * sizeof(int32_t)));
-        c->cap_tiny = cap; c->cap_tiny_ends = cap_ends;
-    }
+    HIPCHK(c->tiny_sc.ensure(std::max<size_t>(n_ends * 2 * (size_t)maxb, (size_t)TINY_MAX_WAVES * 2)));
+    HIPCHK(c->tiny_tpl.ensure(std::max<size_t>(n_ends, 4096) * MAX_T * 2));
     return 0;
 }
 
@@ -909,10 +883,10 @@ static int simple_packed_scan(qcat_ctx* c, KitPtrs kp, const DevKit& hk, size_t 
     const int per = (bs.n + nch - 1) / nch;
     nch = (bs.n + per - 1) / per;                   // (every chunk holds a barcode)
     int rc;
-    if (dbg_rows) { if ((rc = grow(&c->simple_full, &c->cap_simple_full, (size_t)n_tiles * bs.n * 128))) return rc; }
+    if (dbg_rows) { if ((rc = grow(c->simple_full, (size_t)n_tiles * bs.n * 128))) return rc; }
     else {
-        if ((rc = grow(&c->simple_part, &c->cap_simple_part, (size_t)n_tiles * nch * 128))) return rc;
-        if ((rc = grow(&c->simple_redo, &c->cap_simple_redo, n_ends + 1))) return rc;
+        if ((rc = grow(c->simple_part, (size_t)n_tiles * nch * 128))) return rc;
+        if ((rc = grow(c->simple_redo, n_ends + 1))) return rc;
         HIPCHK(hipMemsetAsync(c->simple_redo, 0, sizeof(uint32_t), c->stream));
     }
     uint32_t* full = dbg_rows ? c->simple_full : nullptr;
@@ -952,18 +926,18 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
     const size_t n_ends = (size_t)n * ends;
     if (n_ends >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "batch too large (>= 2^31 read ends)");
 
-    if ((rc = grow(&c->win, &c->cap_win, n_ends * WIN_STRIDE + 512))) return rc;    // + slack: k_job_gather reads whole dwords, k_bs_barcode 84 bytes from any region start
-    if ((rc = grow(&c->wlen, &c->cap_wlen, n_ends))) return rc;
-    if ((rc = grow(&c->wspec, &c->cap_wspec, n_ends))) return rc;
+    if ((rc = grow(c->win, n_ends * WIN_STRIDE + 512))) return rc;    // + slack: k_job_gather reads whole dwords, k_bs_barcode 84 bytes from any region start
+    if ((rc = grow(c->wlen, n_ends))) return rc;
+    if ((rc = grow(c->wspec, n_ends))) return rc;
     // + slack: readers take whole dwords past a region's end -- and, round 5, one dword in FRONT of the first window (a front-padded
     // unit of the bit-sliced barcode kernels fetches from up to BS_PAD_ROWS bases before a region): the windows start WIN2_FRONT words in
-    if ((rc = grow(&c->win2, &c->cap_win2, n_ends * WIN2_WORDS + 64 + WIN2_FRONT))) return rc;
-    if ((rc = grow(&c->recs, &c->cap_recs, n_ends))) return rc;
-    if ((rc = grow(&c->results, &c->cap_reads, (size_t)n))) return rc;
-    if ((rc = grow(&c->counts, &c->cap_buckets, (size_t)hk.n_buckets))) return rc;
+    if ((rc = grow(c->win2, n_ends * WIN2_WORDS + 64 + WIN2_FRONT))) return rc;
+    if ((rc = grow(c->recs, n_ends))) return rc;
+    if ((rc = grow(c->results, (size_t)n))) return rc;
+    if ((rc = grow(c->counts, (size_t)hk.n_buckets))) return rc;
     if (debug) {
-        if ((rc = grow(&c->dbg_tpl, &c->cap_dbg_tpl, n_ends * 2 * MAX_T))) return rc;
-        if (row_stride && (rc = grow(&c->dbg_rows, &c->cap_dbg_rows, n_ends * 2 * row_stride))) return rc;
+        if ((rc = grow(c->dbg_tpl, n_ends * 2 * MAX_T))) return rc;
+        if (row_stride && (rc = grow(c->dbg_rows, n_ends * 2 * row_stride))) return rc;
         HIPCHK(hipMemsetAsync(c->dbg_tpl, 0, n_ends * 2 * MAX_T * 4, c->stream));
         if (row_stride) HIPCHK(hipMemsetD16Async((hipDeviceptr_t)c->dbg_rows, (unsigned short)0x8000, n_ends * 2 * row_stride, c->stream));
     }
@@ -985,8 +959,7 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
     // the path pays while its waves -- one per (read end, template) plus one per (read end, set, barcode) -- fit the chip a few
     // times over: up to TINY_MAX_WAVES of them (tools/tiny_crossover.py: PBC096 wins to ~180 reads, NBD104 to ~700)
     const QOptVal tiny_env = qopt_get(QO_TINY_MAX_ENDS);
-    int tiny_maxb = 1;
-    for (int t = 0; t < hk.nt; ++t) for (int s2 = 0; s2 < 2; ++s2) tiny_maxb = std::max(tiny_maxb, (int)hk.tpl[t].sets[s2].n);
+    const int tiny_maxb = max_set_barcodes(hk);
     const uint64_t tiny_waves = n_ends * (uint64_t)(hk.nt + tiny_maxb * (hk.mode == QCAT_MODE_DUAL ? 2 : 1));
     const bool tiny_fits = tiny_env ? n_ends <= (uint64_t)std::max<long long>(0, atoll(tiny_env)) : tiny_waves <= (uint64_t)TINY_MAX_WAVES;
     const bool tiny = n_ends > 0 && n_ends <= 4096 && tiny_fits && !opt_on(QO_NO_TINY) && hk.mode != QCAT_MODE_SIMPLE && resume_kit_mask < 0 &&
@@ -997,7 +970,7 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
         if ((rc = tiny_buffers(c, (size_t)n_ends, tiny_maxb))) return rc;
         use_packed = false;                        // (no job tables, no lazy windows: the tiny kernels read byte windows)
     }
-    g_fill_defer = n != 0 && !opt_on(QO_NO_FILL_MERGE);
+    FillScope fills(n != 0 && !opt_on(QO_NO_FILL_MERGE));      // (every return before a flush drops what was queued)
     if (!keep_counts) HIPCHK(packed_fill(c->counts, 0, (size_t)hk.n_buckets * 8, c->stream));
     if (n == 0) { HIPCHK(packed_fill_flush(c->stream)); return 0; }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[0], c->stream));   // (an empty batch returned above: its slot holds no marks)
@@ -1012,10 +985,10 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
         c->packed.abs_ready = 0;
         if (g_fill_defer && use_packed && hk.mode != QCAT_MODE_SIMPLE) {
             c->packed.slim = use_packed && !debug && !opt_on(QO_NO_SLIM);     // (packed_prepare sizes the slim buffers)
-            if ((rc = packed_prepare(c->stream, hk, (uint32_t)n_ends, &c->packed))) { g_fill_defer = false; g_fill.n = 0; return set_err(rc, packed_last_error()); }
+            if ((rc = packed_prepare(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
             c->packed.prepared = true;
             if (packed_abs_wanted(hk, (uint32_t)n_ends, true) &&
-                (rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) { g_fill_defer = false; g_fill.n = 0; return set_err(rc, packed_last_error()); }
+                (rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
         }
         HIPCHK(packed_fill_flush(c->stream));
         c->win2_valid = true;
@@ -1032,7 +1005,7 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
         if (use_packed && hk.mode != QCAT_MODE_SIMPLE && !adapter_only && opt_val(QO_PACK_PLANES, 1) != 0 && packed_abs_wanted(hk, (uint32_t)n_ends, true)) {
             if (c->packed.abs_zeroed != (uint32_t)n_ends && (rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
             const uint32_t tiles = ((uint32_t)n_ends + ABS_TILE - 1) / ABS_TILE;
-            uint32_t* cursor = reinterpret_cast<uint32_t*>(c->packed.abs_flags);
+            uint32_t* cursor = reinterpret_cast<uint32_t*>(c->packed.abs_flags.get());
             uint32_t* tile_any = cursor + MAX_T;
             (void)qcat_abs_launch_pack_planes(c->stream, b->bases, b->offsets, n, ends, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0,
                                               c->packed.abs_planes, c->packed.abs_valid, reinterpret_cast<uint8_t*>(tile_any + tiles), tile_any);
@@ -1052,7 +1025,7 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
     if (resume_kit_mask >= 0 && g_fill_defer && use_packed && c->packed.slices_single && hk.mode != QCAT_MODE_SIMPLE) {
         // (a resumed scan -- the second pass of a kit-auto batch: its job tables' fills with the count vector's, one launch)
         c->packed.slim = use_packed && !debug && !opt_on(QO_NO_SLIM);
-        if ((rc = packed_prepare(c->stream, hk, (uint32_t)n_ends, &c->packed))) { g_fill_defer = false; g_fill.n = 0; return set_err(rc, packed_last_error()); }
+        if ((rc = packed_prepare(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
         c->packed.prepared = true;
     }
     HIPCHK(packed_fill_flush(c->stream));               // (a resumed scan: the count vector's fill)
@@ -1117,22 +1090,14 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
             c->midw_ran = false;
             if (only && hk.gap_open == hk.gap_extend && !opt_on(QO_NO_TINY) && !c->force_generic) {
                 constexpr uint32_t MIDW_CAP = 2048;
-                int maxb = 1;
-                for (int t = 0; t < hk.nt; ++t) for (int s2 = 0; s2 < 2; ++s2) maxb = std::max(maxb, (int)hk.tpl[t].sets[s2].n);
-                if (!c->midw_list) {
-                    HIPCHK(q_malloc((void**)&c->midw_list, (MIDW_CAP + 1) * sizeof(uint32_t)));
-                    HIPCHK(q_malloc((void**)&c->midw_tpl, (size_t)MIDW_CAP * 2 * MAX_T * 2 * sizeof(int32_t)));
-                    HIPCHK(q_malloc((void**)&c->midw_recs, (size_t)MIDW_CAP * 2 * sizeof(EndRec)));
-                }
-                if ((size_t)maxb > c->cap_midw_sc) {
-                    (void)hipFree(c->midw_sc); c->midw_sc = nullptr; c->cap_midw_sc = 0;
-                    HIPCHK(q_malloc((void**)&c->midw_sc, (size_t)MIDW_CAP * 2 * 2 * (size_t)maxb * sizeof(int16_t)));
-                    c->cap_midw_sc = (size_t)maxb;
-                }
+                HIPCHK(c->midw_list.ensure(MIDW_CAP + 1));
+                HIPCHK(c->midw_tpl.ensure((size_t)MIDW_CAP * 2 * MAX_T * 2));
+                HIPCHK(c->midw_recs.ensure((size_t)MIDW_CAP * 2));
+                HIPCHK(c->midw_sc.ensure((size_t)MIDW_CAP * 2 * 2 * (size_t)tiny_maxb));
                 uint32_t* count = c->midw_list + MIDW_CAP;
                 HIPCHK(hipMemsetAsync(count, 0, sizeof(uint32_t), c->stream));
                 MidWaveArgs ma{kp, b->bases, b->offsets, n, c->results, c->mid_generic, c->midw_list, count, MIDW_CAP,
-                               c->midw_tpl, c->midw_recs, c->midw_sc, (uint32_t)maxb};
+                               c->midw_tpl, c->midw_recs, c->midw_sc, (uint32_t)tiny_maxb};
                 hipLaunchKernelGGL(k_midw_list, dim3((n + 255) / 256), dim3(256), 0, c->stream, ma);
                 hipLaunchKernelGGL(k_midw_adapter, dim3(1024), dim3(64), 0, c->stream, ma);
                 hipLaunchKernelGGL(k_midw_decide, dim3(MIDW_CAP * 2 / 64), dim3(64), 0, c->stream, ma);
@@ -1195,12 +1160,9 @@ static int fetch_back(qcat_ctx* c, qcat_result* out, uint32_t n_reads, int64_t* 
     }
     if (n_reads != c->last_n_reads || (counts_add && n_buckets != c->last_buckets)) return set_err(QCAT_ERR_ARG, "sizes do not match the last scan");
     HIPCHK(hipSetDevice(c->device));
-    if (need > c->cap_pin_ret) {
+    if (need > c->pin_ret.cap()) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->pin_ret) (void)hipHostFree(c->pin_ret);
-        c->pin_ret = nullptr; c->cap_pin_ret = 0;
-        HIPCHK(hipHostMalloc((void**)&c->pin_ret, need + need / 4 + 4096));
-        c->cap_pin_ret = need + need / 4 + 4096;
+        HIPCHK(c->pin_ret.ensure(need + need / 4 + 4096));
     }
     if (n_reads) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(c->pin_ret, c->results, bytes_rec, hipMemcpyDeviceToHost, c->stream));
     if (counts_add) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(c->pin_ret + off_cnt, c->counts, (size_t)n_buckets * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1308,6 +1270,15 @@ extern "C" void qcat_batch_destroy(qcat_batch* b) {
     delete b;
 }
 
+// the device arrays of a batch of b->n_reads reads and b->n_bases bases (fixed size, the caller's: no generation bump)
+static int batch_alloc(qcat_batch* b, const char* err) {
+    hipError_t e1 = hipMalloc((void**)&b->bases_alloc, b->n_bases + 2 * BATCH_SLACK);
+    if (e1 == hipSuccess) b->bases = b->bases_alloc + BATCH_SLACK;
+    hipError_t e2 = hipMalloc((void**)&b->offsets, ((size_t)b->n_reads + 1) * 8);
+    if (e1 != hipSuccess || e2 != hipSuccess) return set_err(QCAT_ERR_NOMEM, err);
+    return 0;
+}
+
 extern "C" int qcat_batch_info(const qcat_batch* b, uint32_t* n_reads, uint64_t* n_bases) {
     if (!b) return set_err(QCAT_ERR_ARG, "null batch");
     if (n_reads) *n_reads = b->n_reads;
@@ -1326,10 +1297,7 @@ extern "C" int qcat_batch_upload(qcat_ctx* c, const uint8_t* bases, const uint64
     qcat_batch* b = new qcat_batch();
     BatchGuard guard(b);
     b->device = c->device; b->n_reads = n_reads; b->n_bases = offsets[n_reads];
-    hipError_t e1 = hipMalloc((void**)&b->bases_alloc, b->n_bases + 2 * BATCH_SLACK);
-    if (e1 == hipSuccess) b->bases = b->bases_alloc + BATCH_SLACK;
-    hipError_t e2 = hipMalloc((void**)&b->offsets, ((size_t)n_reads + 1) * 8);
-    if (e1 != hipSuccess || e2 != hipSuccess) return set_err(QCAT_ERR_NOMEM, "hipMalloc failed for batch");
+    if (int rc = batch_alloc(b, "hipMalloc failed for batch")) return rc;
     if (b->n_bases) HIPCHK(hipMemcpyAsync(b->bases, bases, b->n_bases, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b->offsets, offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1381,13 +1349,9 @@ static int batch_upload_windows(qcat_ctx* c, const qcat_kit* kit, const uint8_t*
     const uint64_t n = (uint64_t)hk.max_align;
     const bool both = hk.ends == QCAT_ENDS_BOTH;
     const uint64_t keep = whole ? ~0ull : (both ? 2 * n : n);
-    if ((size_t)n_reads + 1 > c->cap_pin_reads) {
-        if (c->pin_offsets) (void)hipHostFree(c->pin_offsets);
-        if (c->pin_len) (void)hipHostFree(c->pin_len);
-        c->pin_offsets = nullptr; c->pin_len = nullptr; c->cap_pin_reads = 0;
-        HIPCHK(hipHostMalloc((void**)&c->pin_offsets, ((size_t)n_reads + 1) * 8));
-        HIPCHK(hipHostMalloc((void**)&c->pin_len, ((size_t)n_reads + 1) * 4));
-        c->cap_pin_reads = (size_t)n_reads + 1;
+    if ((size_t)n_reads + 1 > std::min(c->pin_offsets.cap(), c->pin_len.cap())) {
+        HIPCHK(c->pin_offsets.ensure((size_t)n_reads + 1));
+        HIPCHK(c->pin_len.ensure((size_t)n_reads + 1));
         g_alloc_gen.fetch_add(1);                                      // (kernels of a handful-of-reads call read the staging in place)
     }
     uint64_t total = 0;
@@ -1401,28 +1365,19 @@ static int batch_upload_windows(qcat_ctx* c, const qcat_kit* kit, const uint8_t*
         total += len <= keep ? len : keep;
         c->pin_offsets[r + 1] = total;
     }
-    if (total + 1 > c->cap_pin_bases) {
-        if (c->pin_bases) (void)hipHostFree(c->pin_bases);
-        c->pin_bases = nullptr; c->cap_pin_bases = 0;
-        HIPCHK(hipHostMalloc((void**)&c->pin_bases, total + 1 + 2 * BATCH_SLACK));      // (slack either side like a device batch)
+    if (total + 1 + 2 * BATCH_SLACK > c->pin_bases.cap()) {
+        HIPCHK(c->pin_bases.ensure(total + 1 + 2 * BATCH_SLACK));                        // (slack either side like a device batch)
         memset(c->pin_bases, 0, BATCH_SLACK);
-        c->cap_pin_bases = total + 1;
         g_alloc_gen.fetch_add(1);
     }
     uint8_t* const pin_data = c->pin_bases + BATCH_SLACK;
     // the context's own device staging (the batch is a view of it: one host-buffer call at a time per context)
-    if (total + 2 * BATCH_SLACK > c->cap_hb_bases) {
-        (void)hipFree(c->hb_bases); c->hb_bases = nullptr; c->cap_hb_bases = 0;
-        const size_t want = (total + 2 * BATCH_SLACK) * 5 / 4;
-        if (q_malloc((void**)&c->hb_bases, want) != hipSuccess) return set_err(QCAT_ERR_NOMEM, "hipMalloc failed for batch");
-        c->cap_hb_bases = want;
-    }
-    if ((size_t)n_reads + 1 > c->cap_hb_reads) {
-        (void)hipFree(c->hb_offsets); (void)hipFree(c->hb_len); c->hb_offsets = nullptr; c->hb_len = nullptr; c->cap_hb_reads = 0;
+    if (total + 2 * BATCH_SLACK > c->hb_bases.cap() && c->hb_bases.ensure((total + 2 * BATCH_SLACK) * 5 / 4) != hipSuccess)
+        return set_err(QCAT_ERR_NOMEM, "hipMalloc failed for batch");
+    if ((size_t)n_reads + 1 > std::min(c->hb_offsets.cap(), c->hb_len.cap())) {
         const size_t want = ((size_t)n_reads + 1) * 5 / 4;
-        if (q_malloc((void**)&c->hb_offsets, want * 8) != hipSuccess || q_malloc((void**)&c->hb_len, want * 4) != hipSuccess)
+        if (c->hb_offsets.ensure(want) != hipSuccess || c->hb_len.ensure(want) != hipSuccess)
             return set_err(QCAT_ERR_NOMEM, "hipMalloc failed for batch");
-        c->cap_hb_reads = want;
     }
     uint8_t* const dev_data = c->hb_bases + BATCH_SLACK;
     bool sent = false;                                   // the bases have gone to the device slice by slice
@@ -1447,7 +1402,7 @@ static int batch_upload_windows(qcat_ctx* c, const qcat_kit* kit, const uint8_t*
             std::vector<uint32_t> bound;                 // slice j = reads [bound[j], bound[j + 1])
             bound.push_back(0);
             for (uint64_t at = slice_bytes; at < total; at += slice_bytes) {
-                const uint32_t r = (uint32_t)(std::lower_bound(c->pin_offsets, c->pin_offsets + n_reads, at) - c->pin_offsets);
+                const uint32_t r = (uint32_t)(std::lower_bound(c->pin_offsets.get(), c->pin_offsets + n_reads, at) - c->pin_offsets);
                 if (r > bound.back() && r < n_reads) bound.push_back(r);
             }
             bound.push_back(n_reads);
@@ -1611,10 +1566,7 @@ extern "C" int qcat_batch_synthesize(qcat_ctx* c, const qcat_kit* ckit, const qc
     qcat_batch* b = new qcat_batch();
     BatchGuard guard(b);
     b->device = c->device; b->n_reads = n; b->n_bases = offs[n];
-    hipError_t e1 = hipMalloc((void**)&b->bases_alloc, b->n_bases + 2 * BATCH_SLACK);
-    if (e1 == hipSuccess) b->bases = b->bases_alloc + BATCH_SLACK;
-    hipError_t e2 = hipMalloc((void**)&b->offsets, ((size_t)n + 1) * 8);
-    if (e1 != hipSuccess || e2 != hipSuccess) return set_err(QCAT_ERR_NOMEM, "hipMalloc failed for synthetic batch");
+    if ((rc = batch_alloc(b, "hipMalloc failed for synthetic batch"))) return rc;
     HIPCHK(hipMemcpyAsync(b->offsets, offs.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     if (n) hipLaunchKernelGGL(k_synth_write, dim3(blocks), dim3(256), 0, c->stream, s.p, s.t5, s.t3,
                               (int)s.has5, (int)s.has3, (uint64_t)0, n, b->offsets, b->bases);
@@ -1723,29 +1675,18 @@ static int scan_batch_pipelined(qcat_ctx* c, qcat_kit* kit, const ReadView& rv,
     for (PipeStage& st : p->st) {
         if (&st != &p->st[0] && n_chunks < 2) break;
         size_t need_reads = (size_t)largest + 1, need_bases = (size_t)largest * keep + 2 * BATCH_SLACK;
-        if (need_reads > st.cap_reads && st.cap_reads) need_reads = std::min<size_t>((size_t)chunk + 1, need_reads + need_reads / 2);
-        if (need_bases > st.cap_bases && st.cap_bases) need_bases = std::min<size_t>((size_t)chunk * keep + 2 * BATCH_SLACK, need_bases + need_bases / 2);
-        if (need_reads > st.cap_reads) {
-            if (st.pin_offsets) (void)hipHostFree(st.pin_offsets);
-            if (st.pin_len) (void)hipHostFree(st.pin_len);
-            if (st.pin_results) (void)hipHostFree(st.pin_results);
-            (void)hipFree(st.dev_offsets); (void)hipFree(st.dev_len);
-            st.pin_offsets = nullptr; st.pin_len = nullptr; st.pin_results = nullptr; st.dev_offsets = nullptr; st.dev_len = nullptr; st.cap_reads = 0;
-            HIPCHK(hipHostMalloc((void**)&st.pin_offsets, need_reads * 8));
-            HIPCHK(hipHostMalloc((void**)&st.pin_len, need_reads * 4));
-            HIPCHK(hipHostMalloc((void**)&st.pin_results, need_reads * sizeof(qcat_result)));
-            HIPCHK(hipMalloc((void**)&st.dev_offsets, need_reads * 8));
-            HIPCHK(hipMalloc((void**)&st.dev_len, need_reads * 4));
-            st.cap_reads = need_reads;
-        }
-        if (need_bases > st.cap_bases) {
-            if (st.pin_bases) (void)hipHostFree(st.pin_bases);
-            (void)hipFree(st.dev_bases_alloc);
-            st.pin_bases = nullptr; st.dev_bases_alloc = nullptr; st.cap_bases = 0;
-            HIPCHK(hipHostMalloc((void**)&st.pin_bases, need_bases));
-            HIPCHK(hipMalloc((void**)&st.dev_bases_alloc, need_bases));
-            st.cap_bases = need_bases;
-        }
+        // (the arrays of a group grow together: the smallest capacity stands for the group, 0 after an allocation that failed)
+        const size_t cap_reads = std::min({st.pin_offsets.cap(), st.pin_len.cap(), st.pin_results.cap(), st.dev_offsets.cap(), st.dev_len.cap()});
+        const size_t cap_bases = std::min(st.pin_bases.cap(), st.dev_bases_alloc.cap());
+        if (need_reads > cap_reads && cap_reads) need_reads = std::min<size_t>((size_t)chunk + 1, need_reads + need_reads / 2);
+        if (need_bases > cap_bases && cap_bases) need_bases = std::min<size_t>((size_t)chunk * keep + 2 * BATCH_SLACK, need_bases + need_bases / 2);
+        HIPCHK(st.pin_offsets.ensure(need_reads));
+        HIPCHK(st.pin_len.ensure(need_reads));
+        HIPCHK(st.pin_results.ensure(need_reads));
+        HIPCHK(st.dev_offsets.ensure(need_reads));
+        HIPCHK(st.dev_len.ensure(need_reads));
+        HIPCHK(st.pin_bases.ensure(need_bases));
+        HIPCHK(st.dev_bases_alloc.ensure(need_bases));
     }
     struct TimingOff {                                   // per-kernel events describe one scan, not a chunk train
         qcat_ctx* c; bool was;
@@ -1916,7 +1857,7 @@ static int api_graph_run(qcat_ctx* c, qcat_ctx::ApiGraph& G, qcat_kit* kit, KitO
         if (!done) {                                             // (nothing of the capture ran: the plain launches below do the work)
             (void)hipGetLastError();
             if (G.exec) { (void)hipGraphExecDestroy(G.exec); G.exec = nullptr; }
-            g_fill_defer = false; g_fill.n = 0;
+            FillScope drop(false);                                 // (whatever the capture queued and did not flush)
         }
     }
     if (!done && (rc = enqueue())) return drained(rc);
@@ -1981,10 +1922,7 @@ extern "C" int qcat_scan_debug(qcat_ctx* c, const qcat_kit* ckit,
 
 // the vote's device buffer for nb batches: votes [nb][MAX_T], first voters [nb][MAX_T], chosen slots [nb]
 static int vote_buffer(qcat_ctx* c, size_t nb) {
-    if (c->vote_buf && nb <= c->cap_vote_batches) return 0;
-    if (c->vote_buf) { (void)hipFree(c->vote_buf); c->vote_buf = nullptr; c->cap_vote_batches = 0; }
-    HIPCHK(q_malloc((void**)&c->vote_buf, nb * (2 * MAX_T * 8 + 4) + 16));
-    c->cap_vote_batches = nb;
+    HIPCHK(c->vote_buf.ensure(nb * (2 * MAX_T * 8 + 4) + 16));
     return 0;
 }
 
@@ -1999,7 +1937,7 @@ static int vote_resident(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, unsign
     KitOnDevice* kd = nullptr;
     if ((rc = kit_on_device(kit, c->device, &kd))) return drained(rc);
     if ((rc = vote_buffer(c, 1))) return drained(rc);
-    unsigned long long* d = c->vote_buf;
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(c->vote_buf.get());
     HIPCHK(hipMemsetAsync(d, 0, MAX_T * 8, c->stream));
     HIPCHK(hipMemsetAsync(d + MAX_T, 0xFF, MAX_T * 8, c->stream));
     const uint32_t blocks = std::min<uint32_t>((b->n_reads + 255) / 256, 1024);
@@ -2059,7 +1997,7 @@ static int scan_batch_auto_impl(qcat_ctx* c, const qcat_kit* ckit, const uint8_t
     KitOnDevice* kd = nullptr;
     if ((rc = kit_on_device(kit, c->device, &kd))) return drained(rc);
     if ((rc = vote_buffer(c, nb))) return drained(rc);
-    unsigned long long* d = c->vote_buf;
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(c->vote_buf.get());
     unsigned long long* d_first = d + (size_t)nb * MAX_T;
     int32_t* chosen_dev = reinterpret_cast<int32_t*>(d + 2 * (size_t)nb * MAX_T);
     const uint32_t slot_span = batch_reads ? batch_reads * 2u : 0u;        // read ends per batch (both ends: checked above)
@@ -2068,10 +2006,12 @@ static int scan_batch_auto_impl(qcat_ctx* c, const qcat_kit* ckit, const uint8_t
         // pass 1: every template of every kit against both ends (qcat/scanner_base.py:662-678)
         int e = scan_resident_impl(c, kit, b, false, 0, true);
         if (e) return e;
-        g_fill_defer = true;
-        HIPCHK(packed_fill(d, 0, (size_t)nb * MAX_T * 8, c->stream));
-        HIPCHK(packed_fill(d_first, 0xFF, (size_t)nb * MAX_T * 8, c->stream));
-        HIPCHK(packed_fill_flush(c->stream));
+        {
+            FillScope fills(true);
+            HIPCHK(packed_fill(d, 0, (size_t)nb * MAX_T * 8, c->stream));
+            HIPCHK(packed_fill(d_first, 0xFF, (size_t)nb * MAX_T * 8, c->stream));
+            HIPCHK(packed_fill_flush(c->stream));
+        }
         const uint32_t per = batch_reads ? batch_reads : n_reads;
         const uint32_t blocks = std::min<uint32_t>((per + 255) / 256, batch_reads ? 64 : 1024);
         hipLaunchKernelGGL(k_vote, dim3(blocks, nb), dim3(256), 0, c->stream, kd->kit, c->recs, n_reads, d, d_first, batch_reads);
@@ -2097,12 +2037,9 @@ static int scan_batch_auto_impl(qcat_ctx* c, const qcat_kit* ckit, const uint8_t
     const size_t bytes_rec = (size_t)n_reads * sizeof(qcat_result), bytes_vote = 2 * (size_t)nb * MAX_T * 8 + (size_t)nb * 4;
     const size_t off_vote = (bytes_rec + 63) / 64 * 64, off_cnt = (off_vote + bytes_vote + 63) / 64 * 64;
     const size_t need_ret = off_cnt + (size_t)hk.n_buckets * 8;
-    if (need_ret > c->cap_pin_ret) {
+    if (need_ret > c->pin_ret.cap()) {
         (void)hipStreamSynchronize(c->stream);
-        if (c->pin_ret) (void)hipHostFree(c->pin_ret);
-        c->pin_ret = nullptr; c->cap_pin_ret = 0;
-        HIPCHK(hipHostMalloc((void**)&c->pin_ret, need_ret + need_ret / 4));
-        c->cap_pin_ret = need_ret + need_ret / 4;
+        HIPCHK(c->pin_ret.ensure(need_ret + need_ret / 4));
     }
     HIPCHK_DRAIN(c->stream, hipMemcpyAsync(c->pin_ret, c->results, bytes_rec, hipMemcpyDeviceToHost, c->stream));
     HIPCHK_DRAIN(c->stream, hipMemcpyAsync(c->pin_ret + off_vote, d, bytes_vote, hipMemcpyDeviceToHost, c->stream));
@@ -2172,7 +2109,7 @@ extern "C" int qcat_scan_sequences(qcat_ctx* c, const qcat_kit* ckit, const uint
     if (rc) return rc;
     KitOnDevice* kd = nullptr;
     rc = kit_on_device(kit, c->device, &kd);
-    if (!rc) rc = grow(&c->results, &c->cap_reads, (size_t)n_seqs);
+    if (!rc) rc = grow(c->results, (size_t)n_seqs);
     if (!rc && n_seqs) {
         KitPtrs kp{kd->kit, kd->codes, kd->ids, kd->tables};
         const DevKit& hk = kit->hk.dk;
@@ -2181,8 +2118,7 @@ extern "C" int qcat_scan_sequences(qcat_ctx* c, const qcat_kit* ckit, const uint
         // lane -- every mode: the adapter modes with linear or affine gap costs (k_tiny_adapter / k_tiny_adapter_affine; the
         // barcode waves are linear 1/1 always), simple mode on k_tiny_simple_*.  QCAT_HIP_NO_TINY=1, the generic switch and gap
         // costs beyond WAVE_GAP_MAX: the general kernel, as are calls beyond the size limits of kernels_tiny.inc (option WAVE_MAX)
-        int maxb = 1;
-        for (int t = 0; t < hk.nt; ++t) for (int s2 = 0; s2 < 2; ++s2) maxb = std::max(maxb, (int)hk.tpl[t].sets[s2].n);
+        const int maxb = max_set_barcodes(hk);
         const bool affine = hk.gap_open != hk.gap_extend, simple = hk.mode == QCAT_MODE_SIMPLE;
         const bool gaps_fit = !affine || (hk.gap_open >= 0 && hk.gap_extend >= 0 && hk.gap_open <= WAVE_GAP_MAX && hk.gap_extend <= WAVE_GAP_MAX);
         // (linear gaps in the adapter modes: every call, as before; the configurations that came later: up to a number of waves)
@@ -2196,8 +2132,8 @@ extern "C" int qcat_scan_sequences(qcat_ctx* c, const qcat_kit* ckit, const uint
             const uint32_t nb = (uint32_t)std::max(1, (int)hk.tpl[0].sets[0].n);
             const uint32_t PIECE = std::max<uint32_t>(1u, std::min<uint32_t>(32767u, (uint32_t)(((size_t)64 << 20) / ((size_t)nb * 8))));
             const uint32_t piece = std::min(n_seqs, PIECE);
-            rc = grow(&c->recs, &c->cap_recs, (size_t)piece);
-            if (!rc) rc = grow(&c->tiny_simple, &c->cap_tiny_simple, (size_t)piece * nb * 2);
+            rc = grow(c->recs, (size_t)piece);
+            if (!rc) rc = grow(c->tiny_simple, (size_t)piece * nb * 2);
             for (uint32_t s0 = 0; !rc && s0 < n_seqs; s0 += PIECE) {
                 const uint32_t ns = std::min(PIECE, n_seqs - s0);
                 TinyArgs ta{kp, nullptr, nullptr, b->bases, b->offsets + s0, ns, c->recs, nullptr, nullptr, 0, nullptr, nullptr, 0, 0};
@@ -2209,7 +2145,7 @@ extern "C" int qcat_scan_sequences(qcat_ctx* c, const qcat_kit* ckit, const uint
         } else if (waves) {
             constexpr uint32_t PIECE = 32767;          // (the barcode kernel's grid has (sequence, set) in y: 65535 at most)
             const uint32_t piece = std::min(n_seqs, PIECE);
-            rc = grow(&c->recs, &c->cap_recs, (size_t)piece);
+            rc = grow(c->recs, (size_t)piece);
             if (!rc) rc = tiny_buffers(c, (size_t)piece, maxb);
             for (uint32_t s0 = 0; !rc && s0 < n_seqs; s0 += PIECE) {
                 const uint32_t ns = std::min(PIECE, n_seqs - s0);
