@@ -393,6 +393,35 @@ int  qcat_ctx_fetch_counts(qcat_ctx* ctx, int64_t* counts, int32_t n_buckets);
 void* qcat_ctx_counts_devptr(qcat_ctx* ctx);
 void* qcat_ctx_results_devptr(qcat_ctx* ctx);
 
+/* ---- demultiplexing on the device: stable partition of a resident batch by barcode ----
+ * replaces, for reads that stay in HBM: the per-barcode writers of the reference driver (qcat/cli.py:309-358 -- one output per
+ * barcode, reads in file order) behind its trimming and minimum-length filter (qcat/cli.py:521-530: sequence[trim5p:trim3p],
+ * reads under min_read_length are dropped).  The file path has this in csrc/fastq_host.inc; a pipeline with a basecaller in
+ * front and an aligner behind gets the reads of every barcode as one contiguous run of a new resident batch.
+ * A resident scan has ONE kit: a per-batch kit vote (qcat_scan_batch_auto) has no resident form, so neither has this. */
+/* bins of a partition: [barcode buckets of the count vector .., none, skipped]
+ * = (mode == DUAL ? n_slots*n_slots : n_slots) + 2 */
+int  qcat_kit_partition_bins(const qcat_kit* kit);
+/* Stable partition of a resident batch by the calls of `records`:
+ * out = a NEW resident batch (qcat_batch_info / _download / _destroy, qcat_scan_resident) whose reads are the kept slices of
+ * the input's reads, ordered by (bin, index in the input batch).
+ * Bin of a read: its barcode bucket in the count vector of qcat_kit_count_buckets -- `none` without a call -- and the LAST bin,
+ * and no other, for a read the minimum-length filter drops: bin sizes equal the count vector's barcode, none and skipped entries.
+ * Kept slice: [min(trim5p, len), min(trim3p, len)) when the kit has trim_reads and QCAT_ENDS_BOTH (empty when the second bound
+ * is not above the first), else the whole read; skipped reads are copied like any other, callers ignore the last bin.
+ * records: host pointer to n_reads qcat_result (indices inside the kit's tables, trims >= 0), or NULL = the records of this
+ * context's latest qcat_scan_resident (which must have been a scan of n_reads reads with `kit`; otherwise QCAT_ERR_ARG).
+ * flags: reserved, must be 0.  A batch on another device and a batch that is not whole reads of its own: QCAT_ERR_ARG.
+ * Enqueues on the context's stream, synchronises once (the size of `out`).  The result is the same bytes run after run. */
+int  qcat_batch_partition(qcat_ctx* ctx, const qcat_kit* kit, const qcat_batch* batch,
+                          const qcat_result* records, uint32_t flags, qcat_batch** out);
+/* the latest partition of this context: bin b = reads [bin_first[b], bin_first[b+1]) of `out`
+ * (n_bins + 1 entries); source[i] = index in the input batch of read i of `out` (n_reads entries, may be NULL) */
+int  qcat_ctx_fetch_partition(qcat_ctx* ctx, uint64_t* bin_first, int32_t n_bins, uint32_t* source);
+/* the same two vectors in device memory (uint64 / uint32; owned by ctx until its next partition), for callers that stay in HBM */
+void* qcat_ctx_partition_bins_devptr(qcat_ctx* ctx);
+void* qcat_ctx_partition_source_devptr(qcat_ctx* ctx);
+
 /* the context's HIP stream (hipStream_t): a caller that enqueues its own work on it -- e.g. the
  * RCCL all-reduce of the count vector -- is ordered after the scan and before the next one
  * without a host synchronisation. */

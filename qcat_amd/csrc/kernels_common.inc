@@ -338,6 +338,20 @@ __device__ __forceinline__ bool dev_skipped(const DevKit* k, int64_t len, int tr
     return len < (int64_t)k->min_read_length;
 }
 
+// the barcode bucket of a call in the count vector (update_barcode_count, qcat/scanner_base.py:680-689): the slot of the
+// barcode's id -- dual mode: slot1 * n_slots + slot2 -- for a call with an adapter (simple mode: any call), else `none`
+// (= nbc).  One function for k_finalize, k_count and the bins of qcat_batch_partition (kernels_partition.inc).
+__device__ __forceinline__ int dev_barcode_bucket(const KitPtrs& kp, int nb, int nbc, int bc0, int bc1, int adapter) {
+    const DevKit* k = kp.kit;
+    int slot = nbc;
+    if (bc0 >= 0 && (adapter >= 0 || k->mode == QCAT_MODE_SIMPLE)) {
+        const DevTpl& p = k->tpl[adapter < 0 ? 0 : adapter];
+        slot = kp.ids[p.sets[0].ids_off + bc0];
+        if (k->mode == QCAT_MODE_DUAL) slot = slot * nb + kp.ids[p.sets[1].ids_off + bc1];
+    }
+    return slot;
+}
+
 __global__ void __launch_bounds__(256)
 k_count(KitPtrs kp, const qcat_result* __restrict__ results, const uint64_t* __restrict__ offsets,
         const uint32_t* __restrict__ true_len, uint32_t n_reads, unsigned long long* __restrict__ counts) {
@@ -353,12 +367,7 @@ k_count(KitPtrs kp, const qcat_result* __restrict__ results, const uint64_t* __r
     const int nbc = (k->mode == QCAT_MODE_DUAL) ? nb * nb : nb;
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (uint64_t)gridDim.x * blockDim.x) {
         const qcat_result res = results[r];
-        int slot = nbc;
-        if (res.barcode_idx >= 0 && (res.adapter_idx >= 0 || k->mode == QCAT_MODE_SIMPLE)) {
-            const DevTpl& p = k->tpl[res.adapter_idx < 0 ? 0 : res.adapter_idx];
-            slot = kp.ids[p.sets[0].ids_off + res.barcode_idx];
-            if (k->mode == QCAT_MODE_DUAL) slot = slot * nb + kp.ids[p.sets[1].ids_off + res.barcode2_idx];
-        }
+        int slot = dev_barcode_bucket(kp, nb, nbc, res.barcode_idx, res.barcode2_idx, res.adapter_idx);
         int kslot = nbc + 1 + (res.adapter_idx >= 0 ? k->tpl[res.adapter_idx].kit_slot : k->n_kit_slots);
         const int64_t len = true_len ? (int64_t)true_len[r] : (int64_t)(offsets[r + 1] - offsets[r]);
         if (dev_skipped(k, len, res.trim5p, res.trim3p)) { slot = nbuckets - 1; kslot = -1; }
@@ -515,12 +524,7 @@ k_finalize(KitPtrs kp, const EndRec* __restrict__ recs, const uint64_t* __restri
         }
         dev_store_result(reinterpret_cast<qcat_result*>(s_out) + threadIdx.x, res, trim5, trim3);
         if (counts) {
-            int slot = nbc;
-            if (res.bc0 >= 0 && (res.adapter >= 0 || k->mode == QCAT_MODE_SIMPLE)) {
-                const DevTpl& p = k->tpl[res.adapter < 0 ? 0 : res.adapter];
-                slot = kp.ids[p.sets[0].ids_off + res.bc0];
-                if (k->mode == QCAT_MODE_DUAL) slot = slot * nb + kp.ids[p.sets[1].ids_off + res.bc1];
-            }
+            int slot = dev_barcode_bucket(kp, nb, nbc, res.bc0, res.bc1, res.adapter);
             int kslot = nbc + 1 + (res.adapter >= 0 ? k->tpl[res.adapter].kit_slot : k->n_kit_slots);
             if (dev_skipped(k, len, trim5, trim3)) { slot = nbuckets - 1; kslot = -1; }
             if (lds_hist) { atomicAdd(&hist[slot], 1u); if (kslot >= 0) atomicAdd(&hist[kslot], 1u); }

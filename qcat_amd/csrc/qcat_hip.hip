@@ -37,6 +37,7 @@
 #include "packed_host.inc"
 #include "kernels_static.inc"
 #include "kernels_middle.inc"
+#include "kernels_partition.inc"
 #include "static_registry.inc"
 #include "host_pipeline.inc"
 
@@ -512,6 +513,17 @@ struct qcat_ctx {
     uint32_t absm_last_big = 0, absm_last_128 = 0;                // big tiles / tiles of 128 slots of the latest scan on that path (0: not taken)
     uint32_t last_n_reads = 0;
     int last_buckets = 0;
+    const qcat_kit* last_kit = nullptr;            // the kit of the scan whose records `results` holds (null: none, or a vote only)
+    // qcat_batch_partition (kernels_partition.inc): keys, the radix sort's two (key, read index) buffers, histogram table, block
+    // sums of the scans, slices, the copy's tables; `source` / `bins` belong to the latest partition
+    struct PartScratch {
+        DevBuf<uint32_t> key[2], idx[2], hist, sums32, chunk_first;
+        DevBuf<uint64_t> start, keep, src_pos, sums64, bins;
+        DevBuf<qcat_result> recs;                  // records a caller handed over
+        uint32_t* source = nullptr;                // = idx[passes & 1] of the latest partition
+        uint32_t n_reads = 0;
+        int32_t n_bins = 0;                        // 0: no partition yet
+    } part;
     // device staging of the host-buffer calls (qcat_scan_batch / _auto / _debug, qcat_detect_kit): grown on demand and
     // reused -- a 4000-read batch of the reference driver's call shape spent a third of its call in six hipMalloc / hipFree
     DevBuf<uint8_t> hb_bases;
@@ -607,6 +619,17 @@ template <class T>
 static int grow(DevBuf<T>& buf, size_t need) {
     const hipError_t e = buf.ensure(need);
     return e == hipSuccess ? 0 : set_err(QCAT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+}
+
+// a timed call begins: the next event set of the ring (the caller records ev[0] where its device work starts)
+static void timing_slot(qcat_ctx* c) {
+    c->n_timed = 0;
+    c->ev = nullptr;
+    if (c->timing) {                               // next slot of the ring; a full ring restarts (oldest scans dropped)
+        if (c->ring_used >= qcat_ctx::TIME_RING) c->ring_used = 0;
+        c->ring_marks[c->ring_used] = 0;
+        c->ev = c->evr[c->ring_used++];
+    }
 }
 
 static void mark(qcat_ctx* c, const char* name) {
@@ -943,13 +966,8 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
     }
     c->last_n_reads = n;
     c->last_buckets = hk.n_buckets;
-    c->n_timed = 0;
-    c->ev = nullptr;
-    if (c->timing) {                               // next slot of the ring; a full ring restarts (oldest scans dropped)
-        if (c->ring_used >= qcat_ctx::TIME_RING) c->ring_used = 0;
-        c->ring_marks[c->ring_used] = 0;
-        c->ev = c->evr[c->ring_used++];
-    }
+    c->last_kit = adapter_only ? nullptr : kit;
+    timing_slot(c);
     // the fills of a scan leave as ONE launch in front of the pack kernel (k_fill_multi): count vector, letter flags, and --
     // with the job tables and the adapter tile flags sized here instead of after the pack kernel -- theirs too
     const bool packed_kit = hk.fast_ok && !c->force_generic && packed_supported(hk);
@@ -1480,6 +1498,134 @@ extern "C" int qcat_batch_download(qcat_ctx* c, const qcat_batch* b, uint8_t* ba
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// stable partition of a resident batch by barcode (kernels_partition.inc)
+// ------------------------------------------------------------------------------------------
+static int part_bins_of(const DevKit& hk) {
+    return (hk.mode == QCAT_MODE_DUAL ? hk.n_barcode_slots * hk.n_barcode_slots : hk.n_barcode_slots) + 2;
+}
+extern "C" int qcat_kit_partition_bins(const qcat_kit* k) { return k ? part_bins_of(k->hk.dk) : QCAT_ERR_ARG; }
+
+// records of a caller index the kit's tables on the device: every index inside them, as a scan writes them
+static bool part_records_fit(const DevKit& hk, const qcat_result* recs, uint32_t n) {
+    for (uint32_t r = 0; r < n; ++r) {
+        const qcat_result& q = recs[r];
+        if (q.adapter_idx < -1 || q.adapter_idx >= hk.nt || q.barcode_idx < -1 || q.trim5p < 0 || q.trim3p < 0) return false;
+        if (q.barcode_idx < 0) continue;
+        if (q.adapter_idx < 0 && hk.mode != QCAT_MODE_SIMPLE) continue;              // (no call: the indices are not looked at)
+        const DevTpl& t = hk.tpl[q.adapter_idx < 0 ? 0 : q.adapter_idx];
+        if (q.barcode_idx >= t.sets[0].n) return false;
+        if (hk.mode == QCAT_MODE_DUAL && (q.barcode2_idx < 0 || q.barcode2_idx >= t.sets[1].n)) return false;
+    }
+    return true;
+}
+
+extern "C" int qcat_batch_partition(qcat_ctx* c, const qcat_kit* ckit, const qcat_batch* b, const qcat_result* records,
+                                    uint32_t flags, qcat_batch** out) {
+    if (!c || !ckit || !b || !out) return set_err(QCAT_ERR_ARG, "qcat_batch_partition: null argument");
+    if (flags != 0) return set_err(QCAT_ERR_ARG, "qcat_batch_partition: flags are reserved and must be 0");
+    if (b->device != c->device) return set_err(QCAT_ERR_ARG, "qcat_batch_partition: batch lives on another device than the context");
+    if (b->true_len || b->borrowed)
+        return set_err(QCAT_ERR_ARG, "qcat_batch_partition: the batch holds read windows or borrowed buffers, not whole reads of its own");
+    qcat_kit* kit = const_cast<qcat_kit*>(ckit);
+    const DevKit& hk = kit->hk.dk;
+    const uint32_t n = b->n_reads;
+    if (!records && (c->last_kit != ckit || c->last_n_reads != n))
+        return set_err(QCAT_ERR_ARG, "qcat_batch_partition: records == NULL needs this context's latest qcat_scan_resident to be a scan of "
+                                     "these reads with this kit");
+    if (records && !part_records_fit(hk, records, n))
+        return set_err(QCAT_ERR_ARG, "qcat_batch_partition: a record indexes outside the kit's templates / barcode sets or has a negative trim");
+    if ((size_t)n + 1 >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_partition: batch too large (>= 2^31 reads)");
+    HIPCHK(hipSetDevice(c->device));
+    KitOnDevice* kd = nullptr;
+    int rc = kit_on_device(kit, c->device, &kd);
+    if (rc) return rc;
+    const KitPtrs kp{kd->kit, kd->codes, kd->ids, kd->tables};
+    const uint32_t n_bins = (uint32_t)part_bins_of(hk);
+    const uint32_t passes = qpart::key_passes(n_bins);
+    const uint32_t n_wg = (n + PART_SORT_TILE - 1) / PART_SORT_TILE;
+    const uint64_t max_chunks = qpart::chunks_of(b->n_bases);
+    if (max_chunks >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_partition: batch too large (>= 2^46 bases)");
+
+    // the output: the input's bases are an upper bound, so nothing waits for the device before the copy
+    qcat_batch* ob = new qcat_batch();
+    BatchGuard guard(ob);
+    ob->device = c->device; ob->n_reads = n; ob->n_bases = b->n_bases;
+    if ((rc = batch_alloc(ob, "hipMalloc failed for the partitioned batch"))) return rc;
+
+    auto& P = c->part;
+    P.n_bins = 0; P.source = nullptr;                        // (a failure below leaves no partition behind)
+    for (int i = 0; i < 2; ++i) { if ((rc = grow(P.key[i], n))) return rc; if ((rc = grow(P.idx[i], n))) return rc; }
+    if ((rc = grow(P.hist, (size_t)256 * n_wg))) return rc;
+    if ((rc = grow(P.sums32, part_scan_sums((uint64_t)256 * n_wg)))) return rc;
+    if ((rc = grow(P.sums64, part_scan_sums((uint64_t)n + 1)))) return rc;
+    if ((rc = grow(P.start, n))) return rc;
+    if ((rc = grow(P.keep, n))) return rc;
+    if ((rc = grow(P.src_pos, n))) return rc;
+    if ((rc = grow(P.bins, (size_t)n_bins + 1))) return rc;
+    if ((rc = grow(P.chunk_first, (size_t)max_chunks + 1))) return rc;
+    const qcat_result* recs = c->results;
+    if (records) {
+        if ((rc = grow(P.recs, n))) return rc;
+        if (n) HIPCHK(hipMemcpyAsync(P.recs, records, (size_t)n * sizeof(qcat_result), hipMemcpyHostToDevice, c->stream));
+        recs = P.recs;
+    }
+    timing_slot(c);
+    if (c->timing) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    const uint32_t blocks_n = (n + 255) / 256;
+    // a. keys
+    if (n) hipLaunchKernelGGL(k_part_keys, dim3(std::min<uint32_t>(blocks_n, 8192)), dim3(256), 0, c->stream, kp, recs, b->offsets, n,
+                              P.key[0].get(), P.start.get(), P.keep.get());
+    mark(c, "part_keys");
+    // b. stable order: one to three passes over 8 bits of the bin
+    for (uint32_t p = 0; n && p < passes; ++p) {
+        const uint32_t* kin = P.key[p & 1]; const uint32_t* iin = p ? P.idx[p & 1].get() : nullptr;
+        hipLaunchKernelGGL(k_part_hist, dim3(n_wg), dim3(256), 0, c->stream, kin, n, 8 * p, P.hist.get(), n_wg);
+        part_scan_launch<uint32_t>(P.hist, (uint64_t)256 * n_wg, P.sums32, c->stream);
+        hipLaunchKernelGGL(k_part_scatter, dim3(n_wg), dim3(256), 0, c->stream, kin, iin, n, 8 * p, (const uint32_t*)P.hist.get(), n_wg,
+                           P.key[(p + 1) & 1].get(), P.idx[(p + 1) & 1].get());
+    }
+    const uint32_t* key_sorted = P.key[passes & 1];
+    uint32_t* source = P.idx[passes & 1];
+    mark(c, "part_order");
+    // c. output offsets (they are the output batch's offsets), first read of every bin, first segment of every chunk
+    hipLaunchKernelGGL(k_part_gather, dim3(n / 256 + 1), dim3(256), 0, c->stream, (const uint32_t*)source, (const uint64_t*)P.start.get(),
+                       (const uint64_t*)P.keep.get(), n, ob->offsets, P.src_pos.get());
+    part_scan_launch<uint64_t>(ob->offsets, (uint64_t)n + 1, P.sums64, c->stream);
+    hipLaunchKernelGGL(k_part_bins, dim3(n_bins / 256 + 1), dim3(256), 0, c->stream, key_sorted, n, n_bins, P.bins.get());
+    if (max_chunks) hipLaunchKernelGGL(k_part_chunks, dim3((uint32_t)((max_chunks + 255) / 256)), dim3(256), 0, c->stream,
+                                       (const uint64_t*)ob->offsets, n, P.chunk_first.get(), max_chunks);
+    mark(c, "part_offsets");
+    // d. the copy
+    if (max_chunks) hipLaunchKernelGGL(k_part_copy, dim3((uint32_t)max_chunks), dim3(256), 0, c->stream, (const uint64_t*)ob->offsets,
+                                       (const uint64_t*)P.src_pos.get(), n, (const uint32_t*)P.chunk_first.get(), (const uint8_t*)b->bases, ob->bases);
+    mark(c, "part_copy");
+    uint64_t total = 0;
+    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&total, ob->offsets + n, 8, hipMemcpyDeviceToHost, c->stream));
+    hipError_t es = hipStreamSynchronize(c->stream);
+    if (es == hipSuccess) es = hipGetLastError();
+    if (es != hipSuccess) return set_err(QCAT_ERR_DEVICE, std::string("qcat_batch_partition: ") + hipGetErrorString(es));
+    if (total > b->n_bases) return set_err(QCAT_ERR_DEVICE, "qcat_batch_partition: the slices are longer than the reads");
+    ob->n_bases = total;
+    P.source = source; P.n_reads = n; P.n_bins = (int32_t)n_bins;
+    *out = guard.release();
+    return 0;
+}
+
+extern "C" int qcat_ctx_fetch_partition(qcat_ctx* c, uint64_t* bin_first, int32_t n_bins, uint32_t* source) {
+    if (!c || !bin_first) return set_err(QCAT_ERR_ARG, "null argument");
+    if (!c->part.n_bins) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_partition: no partition on this context");
+    if (n_bins != c->part.n_bins) return set_err(QCAT_ERR_ARG, "bin count does not match the latest partition");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(bin_first, c->part.bins, ((size_t)n_bins + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (source && c->part.n_reads)
+        HIPCHK_DRAIN(c->stream, hipMemcpyAsync(source, c->part.source, (size_t)c->part.n_reads * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+extern "C" void* qcat_ctx_partition_bins_devptr(qcat_ctx* c) { return c && c->part.n_bins ? (void*)c->part.bins.get() : nullptr; }
+extern "C" void* qcat_ctx_partition_source_devptr(qcat_ctx* c) { return c && c->part.n_bins ? (void*)c->part.source : nullptr; }
+
 // --- synthetic reads ------------------------------------------------------------------------
 struct SynthSetup {
     qsynth::Params p;
@@ -1796,6 +1942,7 @@ static int scan_batch_pipelined(qcat_ctx* c, qcat_kit* kit, const ReadView& rv,
                 t_begin - std::chrono::duration<double, std::milli>(t_entry.time_since_epoch()).count(), t_wait, t_prefix, t_compact, t_enqueue,
                 now() - t_loop, now() - t_begin);
     c->last_n_reads = 0;                                 // the context's result buffer holds the last chunk only
+    c->last_kit = nullptr;
     if (rc) return rc;
     if (es != hipSuccess || ec != hipSuccess)
         return set_err(QCAT_ERR_DEVICE, std::string("qcat_scan_batch: ") + hipGetErrorString(es != hipSuccess ? es : ec));
@@ -2167,6 +2314,7 @@ extern "C" int qcat_scan_sequences(qcat_ctx* c, const qcat_kit* ckit, const uint
         if (e != hipSuccess) rc = set_err(QCAT_ERR_DEVICE, std::string("qcat_scan_sequences: ") + hipGetErrorString(e));
     }
     c->last_n_reads = 0;                               // the context's result buffer no longer holds a batch scan
+    c->last_kit = nullptr;
     qcat_batch_destroy(b);
     return rc;
 }

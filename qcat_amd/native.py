@@ -231,6 +231,22 @@ class KitDescriptor(object):
         self.desc = d
 
     @property
+    def n_partition_bins(self):
+        """bins of qcat_batch_partition: [barcode buckets of the count vector .., none, skipped]"""
+        nb = len(self.slot_ids)
+        return (nb * nb if self.mode == "dual" else nb) + 2
+
+    def partition_label(self, b):
+        """what bin ``b`` of a partition stands for: a Barcode.id (dual mode: "id1/id2"), "none" or "skipped" """
+        nb = len(self.slot_ids)
+        nbc = nb * nb if self.mode == "dual" else nb
+        if b >= nbc:
+            return ("none", "skipped")[b - nbc]
+        if self.mode == "dual":
+            return "{}/{}".format(self.slot_ids[b // nb], self.slot_ids[b % nb])
+        return self.slot_ids[b]
+
+    @property
     def n_count_buckets(self):
         nb = len(self.slot_ids)
         # [barcode slots.., none][kit slots.., none][skipped]
@@ -325,6 +341,7 @@ class HipLibrary(object):
             "qcat_kit_create": (C.c_int, [C.POINTER(KitDesc), C.POINTER(vp)]),
             "qcat_kit_destroy": (None, [vp]),
             "qcat_kit_count_buckets": (C.c_int, [vp]),
+            "qcat_kit_partition_bins": (C.c_int, [vp]),
             "qcat_kit_describe": (C.c_int, [vp, C.POINTER(KitInfo)]),
             "qcat_kit_attach_code": (C.c_int, [vp, C.c_char_p, C.c_uint64, C.POINTER(i32), C.POINTER(i32),
                                               C.POINTER(i32), C.POINTER(i32)]),
@@ -358,6 +375,10 @@ class HipLibrary(object):
             "qcat_ctx_fetch_counts": (C.c_int, [vp, vp, i32]),
             "qcat_ctx_counts_devptr": (vp, [vp]),
             "qcat_ctx_results_devptr": (vp, [vp]),
+            "qcat_batch_partition": (C.c_int, [vp, vp, vp, vp, u32, C.POINTER(vp)]),
+            "qcat_ctx_fetch_partition": (C.c_int, [vp, vp, i32, vp]),
+            "qcat_ctx_partition_bins_devptr": (vp, [vp]),
+            "qcat_ctx_partition_source_devptr": (vp, [vp]),
             "qcat_ctx_last_timing": (C.c_int, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
             "qcat_ctx_set_timing": (C.c_int, [vp, C.c_int]),
             "qcat_sg_align": (C.c_int, [vp, vp, vp, vp, vp, u32, i32, i32, vp, i32, vp]),
@@ -564,6 +585,93 @@ class NativeComm(object):
             pass
 
 
+class ResidentBatch(object):
+    """``qcat_batch*``: reads resident in device memory (qcat_batch_upload / _synthesize / _info / _download / _destroy).
+    Made by :meth:`upload` or :meth:`synthesize`, or handed out by :meth:`NativeContext.partition`; owns the handle."""
+
+    def __init__(self, ctx, handle):
+        self.hip = HipLibrary.get()
+        self.ctx = ctx
+        self.handle = handle
+
+    @classmethod
+    def upload(cls, ctx, bases, offsets):
+        """the reads of :func:`pack_reads` (uint8 bases, uint64 offsets[n + 1])"""
+        hip = HipLibrary.get()
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        h = C.c_void_p()
+        hip.check(hip.lib.qcat_batch_upload(ctx.handle, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, C.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def synthesize(cls, ctx, kit, params):
+        """synthetic reads generated on the device (``params``: a :class:`SynthParams`)"""
+        hip = HipLibrary.get()
+        h = C.c_void_p()
+        hip.check(hip.lib.qcat_batch_synthesize(ctx.handle, kit.handle, C.byref(params), C.byref(h)))
+        return cls(ctx, h)
+
+    def info(self):
+        """(reads, bases)"""
+        nr, nb = C.c_uint32(), C.c_uint64()
+        self.hip.check(self.hip.lib.qcat_batch_info(self.handle, C.byref(nr), C.byref(nb)))
+        return int(nr.value), int(nb.value)
+
+    @property
+    def n_reads(self):
+        return self.info()[0]
+
+    @property
+    def n_bases(self):
+        return self.info()[1]
+
+    def download(self, bases=True):
+        """(uint8 bases or None, uint64 offsets[n + 1]) copied back to the host"""
+        n, nb = self.info()
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        out = np.zeros(nb, dtype=np.uint8) if bases else None
+        self.hip.check(self.hip.lib.qcat_batch_download(self.ctx.handle, self.handle, out.ctypes.data if bases and nb else None,
+                                                        offsets.ctypes.data))
+        return out, offsets
+
+    def destroy(self):
+        h = getattr(self, "handle", None)
+        if h:
+            self.hip.lib.qcat_batch_destroy(h)
+            self.handle = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class Partition(object):
+    """What :meth:`NativeContext.partition` returns: ``batch`` (a :class:`ResidentBatch` of the kept slices ordered by bin,
+    then by index in the input), ``bin_first`` (uint64, bins + 1 entries: bin b = reads [bin_first[b], bin_first[b + 1]) of
+    ``batch``) and ``source`` (uint32: index in the input batch of every read of ``batch``)."""
+
+    def __init__(self, batch, bin_first, source):
+        self.batch, self.bin_first, self.source = batch, bin_first, source
+        self._host = None
+
+    @property
+    def n_bins(self):
+        return len(self.bin_first) - 1
+
+    def reads(self, b):
+        """the reads of bin ``b`` as a list of bytes (the batch is downloaded once, at the first call)"""
+        if self._host is None:
+            bases, offsets = self.batch.download()
+            self._host = (bases.tobytes(), offsets.tolist())
+        raw, offsets = self._host
+        return [raw[offsets[i]:offsets[i + 1]] for i in range(int(self.bin_first[b]), int(self.bin_first[b + 1]))]
+
+
 class NativeContext(object):
     """``qcat_ctx*`` handle: one device, one stream; not re-entrant."""
 
@@ -582,6 +690,44 @@ class NativeContext(object):
             except Exception:
                 pass
             self.handle = None
+
+    def scan_resident(self, kit, batch, fetch=True):
+        """qcat_scan_resident of a :class:`ResidentBatch`: (records, counts) -- or None with ``fetch=False``: records and counts
+        stay on the device (the next :meth:`partition` of ``batch`` takes them from there)."""
+        handle = kit.handle                            # (a background compile may swap the kit's handle: remember the one that ran)
+        self.hip.check(self.hip.lib.qcat_scan_resident(self.handle, handle, batch.handle))
+        self._resident_scan = (kit, handle, batch)
+        if not fetch:
+            return None
+        n = batch.n_reads
+        recs = np.zeros(n, dtype=RESULT_DTYPE)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_results(self.handle, recs.ctypes.data, n))
+        nb = self.hip.lib.qcat_kit_count_buckets(handle)
+        counts = np.zeros(nb, dtype=np.int64)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_counts(self.handle, counts.ctypes.data, nb))
+        return recs, counts
+
+    def partition(self, kit, batch, records=None):
+        """qcat_batch_partition: the reads of ``batch`` grouped by barcode -- a :class:`Partition`.  ``records``: a RESULT_DTYPE
+        array with one record per read, or None for the records of this context's latest :meth:`scan_resident` (of ``batch``
+        with ``kit``)."""
+        handle = kit.handle
+        last = getattr(self, "_resident_scan", None)
+        if records is None and last is not None and last[0] is kit:
+            handle = last[1]
+        if records is not None:
+            records = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
+            if len(records) != batch.n_reads:
+                raise RuntimeError("partition: {} records for a batch of {} reads".format(len(records), batch.n_reads))
+        out = C.c_void_p()
+        self.hip.check(self.hip.lib.qcat_batch_partition(self.handle, handle, batch.handle,
+                                                         records.ctypes.data if records is not None else None, 0, C.byref(out)))
+        part = ResidentBatch(self, out)
+        n_bins = self.hip.lib.qcat_kit_partition_bins(handle)
+        bin_first = np.zeros(n_bins + 1, dtype=np.uint64)
+        source = np.zeros(part.n_reads, dtype=np.uint32)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_partition(self.handle, bin_first.ctypes.data, n_bins, source.ctypes.data))
+        return Partition(part, bin_first, source)
 
     def detect_kit(self, kit, bases, offsets):
         """per-template (votes, first voting read) of qcat_detect_kit."""

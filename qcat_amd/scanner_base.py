@@ -228,12 +228,12 @@ class BarcodeScanner(object):
                                     min_quality=self.min_quality, ends=ends, scan_middle=scan_middle,
                                     min_read_length=min_read_length, trim=trim)
 
-    def _native_kit(self, layouts, qcat_config, ends):
+    def _native_kit(self, layouts, qcat_config, ends, min_read_length=0, trim=False):
         key = (tuple(id(l) for l in layouts), qcat_config.fingerprint(), ends, self.min_quality,
-               bool(self.scan_middle_adapter), native.get_r1_rule())
+               bool(self.scan_middle_adapter), native.get_r1_rule(), int(min_read_length), bool(trim))
         kit = self._kits.get(key)
         if kit is None:
-            kit = native.NativeKit(self.descriptor(layouts, qcat_config, ends))
+            kit = native.NativeKit(self.descriptor(layouts, qcat_config, ends, min_read_length=min_read_length, trim=trim))
             self._kits[key] = kit
         return kit
 
@@ -440,6 +440,38 @@ class BarcodeScanner(object):
             return None
         recs, _slot = got
         return self._records_to_dicts(recs[:n], self.layouts)
+
+    def demux_batch(self, read_sequences, trim=False, min_read_length=0, qcat_config=None):
+        """Demultiplex a batch on the device: upload, scan, stable partition by barcode (qcat_batch_partition) -- what the
+        reference driver's per-barcode writers do with a file (``qcat/cli.py:309-358`` behind ``:521-530``), for reads that
+        live in device memory.  Returns ``{bin label: [(index in read_sequences, sequence), ...]}`` with the non-empty bins in
+        bin order: the Barcode ids in slot order (dual mode: "id1/id2"), then "none", then "skipped" (reads the minimum-length
+        filter drops); sequences are trimmed to ``[trim5p:trim3p]`` under ``trim``.  The scanner must have ONE kit (or be a
+        simple scanner): a resident scan has one kit, and kit auto votes per batch."""
+        if qcat_config is None:
+            qcat_config = config.qcatConfig()
+        if not self.layouts and self._native_mode != "simple":
+            raise IndexError("list index out of range")
+        kits = sorted(set(l.kit for l in self.layouts))
+        if self._native_mode != "simple" and len(kits) != 1:
+            raise ValueError("demux_batch needs a scanner with a fixed kit: the partition follows ONE resident scan, which has one "
+                             "kit, and kit auto votes per batch (this scanner holds %d kits)" % len(kits))
+        kit = self._native_kit(self.layouts, qcat_config, native.ENDS_BOTH, min_read_length=min_read_length, trim=trim)
+        ctx = self._context()
+        bases, offsets = native.pack_reads(read_sequences)
+        batch = native.ResidentBatch.upload(ctx, bases, offsets)
+        try:
+            ctx.scan_resident(kit, batch, fetch=False)
+            part = ctx.partition(kit, batch)
+        finally:
+            batch.destroy()
+        out = {}
+        source = part.source.tolist()
+        for b in np.flatnonzero(np.diff(part.bin_first.astype(np.int64)) > 0).tolist():
+            first = int(part.bin_first[b])
+            out[kit.descriptor.partition_label(b)] = [(source[first + i], seq.decode("latin-1")) for i, seq in enumerate(part.reads(b))]
+        part.batch.destroy()
+        return out
 
     @staticmethod
     def update_barcode_count(result, barcode_count):

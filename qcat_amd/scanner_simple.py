@@ -91,8 +91,9 @@ class BarcodeScannerSimple(BarcodeScanner):
                                     min_quality=self.min_quality, ends=ends, scan_middle=False,
                                     min_read_length=min_read_length, trim=trim)
 
-    def _native_kit(self, layouts, qcat_config, ends):
-        return super(BarcodeScannerSimple, self)._native_kit([self._simple_layout], qcat_config, ends)
+    def _native_kit(self, layouts, qcat_config, ends, min_read_length=0, trim=False):
+        return super(BarcodeScannerSimple, self)._native_kit([self._simple_layout], qcat_config, ends,
+                                                             min_read_length=min_read_length, trim=trim)
 
     def _records_to_dicts(self, recs, layouts):
         out = []
