@@ -1,7 +1,7 @@
 // abs_mid_kernels.hip -- the bit-sliced interior adapter scan of --detect-middle (kernels_abs_mid.inc) in a translation unit
 // of its own: __graft_entry__.build() compiles this file with -Dqk=qk_absmid -Dqabs=qabs_mid -DQCAT_ABS_NI=14 (row indices of
 // interiors up to 16 384 rows; abs_kernels.hip keeps the eight index planes of the read ends' windows) and qcat_hip.hip
-// reaches the kernels through the extern "C" launchers below (declared in qcat_hip.hip beside middle_packed).
+// reaches the kernels through the extern "C" launchers below (declared in middle_host.inc, which launches them from middle_packed).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 

@@ -37,8 +37,7 @@ constexpr int ABSM_TILE = 2048;
 #endif
 constexpr int ABSM_R = QCAT_ABS_R;
 constexpr int ABSM_GY = 8;                         // workgroups of k_absmid_planes per big tile
-constexpr int ABSM_C2_SLACK = 1040;                // dwords addressable before / after the packed batch: a row block of an alignment that
-                                                   // has not started points up to 16 384 + 31 bases outside its interior
+// (ABSM_C2_SLACK, the dwords addressable on either side of the packed batch: kernels_middle.inc, beside AbsMidArgs)
 
 // 16 codes (one per byte) -> two bits per code
 __device__ __forceinline__ uint32_t absm_pack2(const uint32_t (&c)[4]) {

@@ -22,7 +22,7 @@
 // forward one fails, which gives the same "hit on either" answer.
 // Reads whose interior is longer than 16 384 nt, and kits with a template that has no generated
 // static-letter kernel, keep the general int32 kernel k_scan_middle.
-// Included by qcat_hip.hip after kernels_static.inc.
+// Included by qcat_hip.hip after kernels_static.inc; the host side -- scratch and launch sequence -- is middle_host.inc.
 
 namespace qk {
 
@@ -143,6 +143,8 @@ struct MiddleAdapterArgs {
 
 // parameter block of the bit-sliced interior adapter scan (kernels_abs_mid.inc; launched through abs_mid_kernels.hip).
 // A "big tile" = 2048 consecutive slots of the sorted M-ends = sixteen tiles of 128.
+constexpr int ABSM_C2_SLACK = 1040;                // dwords addressable before / after the packed batch (c2): a row block of an alignment that
+                                                   // has not started points up to 16 384 + 31 bases outside its interior
 struct AbsMidArgs {
     const uint8_t* bases;
     const uint64_t* offsets;

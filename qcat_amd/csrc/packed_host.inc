@@ -2,7 +2,7 @@
 // streams that let independent launches overlap, and the three phases
 //     packed_prepare  (job tables) -> packed_adapter (all templates, k_adapter_finish)
 //                                  -> packed_barcode (job sort, tile images, barcode kernels, select)
-// shared by the main scan (packed_scan) and the interior scan of --detect-middle (qcat_hip.hip).
+// shared by the main scan (packed_scan) and the interior scan of --detect-middle (middle_host.inc).
 // Included by qcat_hip.hip after kernels_packed.inc (and by jit_prelude.inc for the struct layouts).
 
 #include "dev_buf.h"

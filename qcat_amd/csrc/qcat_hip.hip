@@ -66,6 +66,13 @@ static int set_err(int rc, const std::string& m) { g_err = m; return rc; }
         }                                                                                    \
     } while (0)
 
+// room for `need` elements in a scratch buffer of the context, or this layer's out-of-memory error
+template <class T>
+static int grow(DevBuf<T>& buf, size_t need) {
+    const hipError_t e = buf.ensure(need);
+    return e == hipSuccess ? 0 : set_err(QCAT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+}
+
 extern "C" const char* qcat_last_error(void) { return g_err.c_str(); }
 extern "C" int qcat_abi_version(void) { return QCAT_ABI_VERSION; }
 extern "C" const char* qcat_backend(void) { return "hip"; }
@@ -465,6 +472,9 @@ struct BatchGuard {
     BatchGuard& operator=(const BatchGuard&) = delete;
 };
 
+// the interior scan of --detect-middle on a resident batch: its scratch (MiddleScratch) and launch sequence
+#include "middle_host.inc"
+
 // ------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------
@@ -492,25 +502,7 @@ struct qcat_ctx {
     HostPipeline* pipe = nullptr;                  // chunked host-buffer scans (host_pipeline.inc), created on first use
     std::vector<qcat_ctx*> helpers;                // contexts of the kit-auto file loop's other workers (fastq_host.inc), created on first use
     PackedScratch packed;
-    // packed --detect-middle (kernels_middle.inc): M-end sort tables and per-slot arrays
-    DevBuf<MidTables> mid_tables;                                 // (allocated once)
-    DevBuf<uint8_t> mid_generic;
-    DevBuf<uint32_t> mid_slot;
-    DevBuf<uint32_t> mid_sorted; DevBuf<int32_t> mid_len, mid_fallback;
-    DevBuf<uint32_t> mid_win2; DevBuf<uint8_t> mid_wspec;         // the M-ends' first window at two bits per code + flags (k_mid_windows)
-    DevBuf<EndRec> mid_recs; DevBuf<AdapterBest> mid_bests;
-    // ... its bit-sliced adapter scan (kernels_abs_mid.inc): per big tile of 2048 slots [rows, padding zone, kit, first row: 4 x tiles]
-    // [nonempty, invalid: 2 x 64 x tiles] [cursors: MAX_T], the per-128 flags, letter planes and not-started masks
-    DevBuf<uint32_t> absm_tiles;
-    DevBuf<uint8_t> absm_need;
-    DevBuf<uint2> absm_planes;
-    DevBuf<uint32_t> absm_ns;
-    DevBuf<uint32_t> absm_c2;                                     // the batch at two bits per base (with ABSM_C2_SLACK dwords on either side)
-    DevBuf<uint8_t> absm_rspec;
-    DevBuf<uint4> absm_sinfo;                                     // per slot: position / strand, length, special flag
-    hipStream_t absm_stream = nullptr; hipEvent_t absm_go = nullptr, absm_done = nullptr;      // the packed batch beside the read ends' kernels
-    bool absm_codes_early = false;                                // this scan's k_absmid_codes is in flight on absm_stream
-    uint32_t absm_last_big = 0, absm_last_128 = 0;                // big tiles / tiles of 128 slots of the latest scan on that path (0: not taken)
+    MiddleScratch middle;                          // the interior scan of --detect-middle (middle_host.inc)
     uint32_t last_n_reads = 0;
     int last_buckets = 0;
     const qcat_kit* last_kit = nullptr;            // the kit of the scan whose records `results` holds (null: none, or a vote only)
@@ -548,9 +540,6 @@ struct qcat_ctx {
     DevBuf<uint2> simple_part;
     DevBuf<uint32_t> simple_redo;
     DevBuf<uint32_t> simple_full;
-    // --detect-middle: the reads the packed interior scan leaves (long interiors) on the same kernels (k_midw_*)
-    DevBuf<uint32_t> midw_list; DevBuf<int32_t> midw_tpl; DevBuf<EndRec> midw_recs; DevBuf<int16_t> midw_sc;    // (the first three: allocated once)
-    bool midw_ran = false;
     // debug buffers
     DevBuf<int32_t> dbg_tpl;
     DevBuf<int16_t> dbg_rows;
@@ -593,10 +582,8 @@ extern "C" void qcat_ctx_destroy(qcat_ctx* c) {
     if (c->api_graph.exec) (void)hipGraphExecDestroy(c->api_graph.exec);
     if (c->scan_graph.exec) (void)hipGraphExecDestroy(c->scan_graph.exec);
     packed_scratch_free(&c->packed);
+    middle_scratch_free(&c->middle);
     pipeline_free(c->pipe);
-    if (c->absm_stream) (void)hipStreamDestroy(c->absm_stream);
-    if (c->absm_go) (void)hipEventDestroy(c->absm_go);
-    if (c->absm_done) (void)hipEventDestroy(c->absm_done);
     if (c->ev_ready) for (int r = 0; r < qcat_ctx::TIME_RING; ++r) for (int i = 0; i <= MAX_TIMED; ++i) (void)hipEventDestroy(c->evr[r][i]);
     (void)hipStreamDestroy(c->stream);
     delete c;                                      // (every scratch buffer frees itself: dev_buf.h)
@@ -612,13 +599,6 @@ extern "C" int qcat_ctx_set_timing(qcat_ctx* c, int enabled) {
     c->timing = enabled != 0;
     c->ring_used = 0; c->n_timed = 0; c->ev = nullptr;
     return 0;
-}
-
-// room for `need` elements in a scratch buffer of the context, or this layer's out-of-memory error
-template <class T>
-static int grow(DevBuf<T>& buf, size_t need) {
-    const hipError_t e = buf.ensure(need);
-    return e == hipSuccess ? 0 : set_err(QCAT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
 }
 
 // a timed call begins: the next event set of the ring (the caller records ev[0] where its device work starts)
@@ -640,243 +620,9 @@ static void mark(qcat_ctx* c, const char* name) {
     c->ring_marks[c->ring_used - 1] = c->n_timed;
 }
 
-// packed --detect-middle is possible when every template has a generated static-letter adapter
-// kernel (all built-in kits) and the kit's slots fit the sort tables
-static bool middle_packed_ok(const DevKit& hk) {
-    if (!hk.adapter_f16 || hk.n_kit_slots > MID_MAX_KITS || opt_on(QO_MIDDLE_GENERIC)) return false;
-    // the interior kernel carries up to PK_ROWS + 63 rows of bias inside a block plus the offset of its
-    // last-row keys (kernels_middle.inc): g * ((152 + 63 + 128 + 64) - (160 + 128)) + 1 more than a window
-    if (hk.adapter_f16_headroom < hk.gap_open * 119 + 1) return false;
-    for (int t = 0; t < hk.nt; ++t) if (hk.tpl[t].static_kernel < 0) return false;
-    return true;
-}
-
-// the bit-sliced interior adapter scan (kernels_abs_mid.inc, abs_mid_kernels.hip)
-extern "C" void qcat_absmid_prepare(void* stream, const void* args, uint32_t* win2, uint8_t* wspec, int what);
-extern "C" int qcat_absmid_launch(int id, int waves, unsigned grid, void* stream, const void* args);
-
-// kit slots whose templates all have a two-stage bit-sliced plan (the built-in kits' single-template plans)
-static uint32_t absmid_kit_mask(const DevKit& hk) {
-    if (!hk.abs_ok) return 0u;
-    uint32_t mask = 0u, bad = 0u;
-    for (int t = 0; t < hk.nt; ++t) {
-        const int ks = hk.tpl[t].kit_slot, sk = hk.tpl[t].static_kernel;
-        if (ks < 0 || ks >= 32) continue;
-        if (sk >= 0 && sk < QCAT_JIT_BASE && qcat_absmid_launch(sk, 2, 0, nullptr, nullptr)) mask |= 1u << ks; else bad |= 1u << ks;
-    }
-    return mask & ~bad;
-}
-
-// slots of the packed interior scan of n reads, and will its adapter scan run bit-sliced (kit mask != 0)?
-static size_t middle_slots(const DevKit& hk, uint32_t n) {
-    return ((size_t)2 * n + (size_t)hk.n_kit_slots * MID_CLASSES * PK_TILE + PK_TILE - 1) / PK_TILE * PK_TILE;
-}
-static uint32_t absmid_wanted(const DevKit& hk, uint32_t n) {
-    const QOptVal amin = qopt_get(QO_MIDDLE_ABS_MIN);
-    // from 1.25 big tiles of 2048 slots per CU (330 k reads on 256 CUs): below that the binary16 kernel's 3 us per thousand interiors
-    // beat a tile's sequential walk (tools/r04_absmid_sizes.sh, profiles/r04_ab_absmid_sizes.txt)
-    const size_t min_slots = amin ? (size_t)atoll(amin) : (size_t)abs_cu_count() * 2048 * 5 / 4;
-    if (opt_on(QO_MIDDLE_NO_ABS) || middle_slots(hk, n) < min_slots) return 0u;
-    return absmid_kit_mask(hk);
-}
-constexpr size_t ABSM_C2_SLACK_HOST = 1040;                                     // = ABSM_C2_SLACK (kernels_abs_mid.inc)
-
-// QCAT_HIP_MIDDLE_ABS_EARLY=1 (A/B switch, off by default): the batch at two bits per base (k_absmid_codes) at the start of a
-// --detect-middle scan on a stream of its own, beside the read ends' kernels -- it needs the reads only; middle_packed waits
-// for absm_done.  Measured at 1 M reads: the interior phase loses the kernel's 0.12 ms, k_pack_windows and the plane kernel of
-// the read ends -- bound by memory themselves -- gain 0.08 + 0.06 ms: 5.14 ms per step either way.
-static int absmid_codes_early(qcat_ctx* c, const DevKit& hk, const qcat_batch* b, uint32_t n) {
-    c->absm_codes_early = false;
-    if (!((opt_is_set(QO_MIDDLE_ABS_EARLY) && opt_val(QO_MIDDLE_ABS_EARLY, 0) == 1))) return 0;
-    if (!absmid_wanted(hk, n)) return 0;
-    int rc;
-    if (!c->absm_stream) {
-        HIPCHK(hipStreamCreateWithFlags(&c->absm_stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&c->absm_go, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->absm_done, hipEventDisableTiming));
-    }
-    if ((rc = grow(c->absm_c2, (size_t)(b->n_bases / 16) + 4 + 2 * ABSM_C2_SLACK_HOST))) return rc;
-    if ((rc = grow(c->absm_rspec, (size_t)n + 1))) return rc;
-    AbsMidArgs am{};
-    am.bases = b->bases; am.offsets = b->offsets; am.max_align = hk.max_align; am.n_bases = b->n_bases; am.n_reads = n;
-    am.c2 = c->absm_c2 + ABSM_C2_SLACK_HOST; am.rspec = c->absm_rspec;
-    HIPCHK(hipEventRecord(c->absm_go, c->stream));                 // (after whatever the stream holds: the previous scan's readers of c2)
-    HIPCHK(hipStreamWaitEvent(c->absm_stream, c->absm_go, 0));
-    HIPCHK(hipMemsetAsync(c->absm_rspec, 0, (size_t)n + 1, c->absm_stream));
-    qcat_absmid_prepare(c->absm_stream, &am, nullptr, nullptr, 1);
-    HIPCHK(hipEventRecord(c->absm_done, c->absm_stream));
-    c->absm_codes_early = true;
-    return 0;
-}
-
-// the interior scan of every called read on the packed kernels (kernels_middle.inc); leaves
-// c->mid_generic[r] = 1 for reads it could not take (interior longer than the length classes)
-static int middle_packed(qcat_ctx* c, KitPtrs kp, const DevKit& hk, const qcat_batch* b, uint32_t n) {
-    hipStream_t st = c->stream;
-    int rc;
-    const size_t slots = middle_slots(hk, n);
-    if (slots >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "batch too large for the packed interior scan");
-    HIPCHK(c->mid_tables.ensure(1));
-    if ((rc = grow(c->mid_generic, (size_t)n))) return rc;
-    if ((rc = grow(c->mid_slot, (size_t)n))) return rc;
-    HIPCHK(c->mid_win2.ensure(slots * WIN2_WORDS + 64));
-    HIPCHK(c->mid_wspec.ensure(slots + 4));
-    HIPCHK(c->mid_sorted.ensure(slots));
-    HIPCHK(c->mid_len.ensure(slots));
-    HIPCHK(c->mid_fallback.ensure(slots));
-    HIPCHK(c->mid_recs.ensure(slots));
-    if ((rc = grow(c->mid_bests, slots * (size_t)hk.nt))) return rc;
-    // the fills of the interior scan leave as two k_fill_multi launches (round 5; thirteen memsets of 5-7 us each before):
-    // the slot tables here, the job tables / sorted list / redo count / letter flags / tile cursors before the adapter phase
-    const bool merge_fills = !opt_on(QO_NO_FILL_MERGE);
-    {
-        FillScope fills(merge_fills);
-        HIPCHK(packed_fill(c->mid_tables, 0, sizeof(MidTables), st));
-        HIPCHK(packed_fill(c->mid_slot, 0xFF, (size_t)n * 4, st));
-        HIPCHK(packed_fill(c->mid_sorted, 0xFF, slots * 4, st));
-        HIPCHK(packed_fill(c->mid_len, 0, slots * 4, st));
-        HIPCHK(packed_fill(c->mid_fallback, 0, slots * 4, st));
-        HIPCHK(packed_fill_flush(st));
-    }
-    const uint32_t rblocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_mid_count, dim3(rblocks), dim3(256), 0, st, kp.kit, b->offsets, n, c->results, c->mid_tables, c->mid_generic);
-    hipLaunchKernelGGL(k_mid_offsets, dim3(1), dim3(1024), 0, st, c->mid_tables);
-    hipLaunchKernelGGL(k_mid_scatter, dim3((n + 256 * MID_SCAT - 1) / (256 * MID_SCAT)), dim3(256), 0, st,
-                       kp.kit, b->offsets, n, c->results, c->mid_tables, c->mid_sorted, c->mid_len, c->mid_fallback, c->mid_slot);
-    // adapter phase: one launch per template (tiles of other kits record "did not compete"), the
-    // launches of a scan run concurrently
-    PackedScratch* sc = &c->packed;
-    // round 4: the interiors' first window at two bits per code, so that their whole-window barcode jobs -- nearly all of
-    // them -- run on the bit-sliced barcode kernels (QCAT_HIP_MIDDLE_NO_BITSLICE=1: binary16 kernels as before)
-    const bool mid_bs = !opt_on(QO_MIDDLE_NO_BITSLICE);
-    // (with the bit-sliced adapter scan below the windows come from its packed batch instead: k_absmid_windows.  k_mid_windows beside
-    //  the adapter kernels was measured and lost: those fill the register files, each of their waves walks ONE tile, and a wave that
-    //  starts late is the kernel's tail; beside the preparation chain -- kernels that wait for memory like itself -- it gained 0.02 ms)
-    auto launch_mid_windows = [&](hipStream_t q) {
-        const uint64_t wthreads = (uint64_t)slots * 16;           // (sixteen lanes per slot; every slot's flag byte is stored, no fill)
-        hipLaunchKernelGGL(k_mid_windows, dim3((uint32_t)((wthreads + 255) / 256)), dim3(256), 0, q, b->bases, b->offsets, hk.max_align,
-                           c->mid_sorted, (uint32_t)slots, c->mid_win2, c->mid_wspec);
-    };
-    sc->wspec = mid_bs ? c->mid_wspec : nullptr;          // (null: no letter flags, no bit-sliced classes)
-    sc->win2 = mid_bs ? c->mid_win2 : nullptr;
-    sc->win = c->win;                                     // (never read: the job regions come from win2, `lazy`)
-    sc->lazy = mid_bs;
-    sc->slim = false;                                     // ... and the barcode results stay in the interior's own records
-    FillScope fills(merge_fills);                          // (flushed in front of the adapter phase below; every return before drops the list)
-    if ((rc = packed_prepare(st, hk, (uint32_t)slots, sc))) return set_err(rc, packed_last_error());
-    const uint32_t tiles = (uint32_t)(slots / PK_TILE);
-    // round 4: the adapter scan of the interiors in bit-sliced form (kernels_abs_mid.inc) from QCAT_HIP_MIDDLE_ABS_MIN slots
-    // (default: one big tile of 2048 slots per CU); QCAT_HIP_MIDDLE_NO_ABS=1: the binary16 kernel for every tile as before.
-    // The binary16 kernel then only takes the tiles of 128 slots flagged in absm_need.
-    AbsMidArgs am{};
-    bool use_absm = false;
-    c->absm_last_big = 0; c->absm_last_128 = 0;
-    {
-        const uint32_t kmask = absmid_wanted(hk, n);
-        if (kmask) {
-            const uint32_t big = (uint32_t)((slots + 2047) / 2048);
-            // rows of all big tiles together: every tile as long as its longest interior -- the mean of the interiors plus
-            // the width of the length classes a tile spans; a tile beyond the room falls back to the binary16 kernel
-            const QOptVal rcap = qopt_get(QO_MIDDLE_ABS_ROWS);         // (tests: a plane buffer that is too small)
-            size_t rows = rcap ? (size_t)atoll(rcap)
-                               : std::min<size_t>((size_t)1 << 30, (size_t)(2 * b->n_bases / 2048) * 5 / 4 + (size_t)big * 128 + 16384 + 64);
-            if (!rcap && rows * 64 > c->absm_planes.cap()) {
-                // planes + not-started masks are 768 bytes per row (~0.9 bytes per base of the batch): never more than a quarter
-                // of the device memory that is free right now -- the big tiles beyond the room fall back to the binary16 kernel
-                // per tile (k_absmid_scan: row_cap), which needs none of it
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) rows = std::min(rows, std::max<size_t>(16384, free_b / 4 / 768));
-            }
-            const size_t tw = (size_t)big * (4 + 128) + MAX_T;
-            if ((rc = grow(c->absm_tiles, tw))) return rc;
-            if ((rc = grow(c->absm_need, (size_t)tiles + 16))) return rc;
-            if ((rc = grow(c->absm_planes, rows * 64))) return rc;
-            if ((rc = grow(c->absm_ns, rows * 64))) return rc;
-            constexpr size_t C2_SLACK = ABSM_C2_SLACK_HOST;
-            const bool early = c->absm_codes_early;                             // (absmid_codes_early: the packed batch is on its way)
-            c->absm_codes_early = false;
-            if (!early) {
-                if ((rc = grow(c->absm_c2, (size_t)(b->n_bases / 16) + 4 + 2 * C2_SLACK))) return rc;
-                if ((rc = grow(c->absm_rspec, (size_t)n + 1))) return rc;
-            }
-            if ((rc = grow(c->absm_sinfo, slots))) return rc;
-            uint32_t* w = c->absm_tiles;
-            am.bases = b->bases; am.offsets = b->offsets; am.msorted = c->mid_sorted; am.mlen = c->mid_len; am.mt = c->mid_tables;
-            am.max_align = hk.max_align; am.n_tiles = big; am.slot_cap = (uint32_t)slots; am.nt = hk.nt; am.kit_mask = kmask;
-            am.t_rows = (int32_t*)w; am.t_pz = (int32_t*)(w + big); am.t_kit = (int32_t*)(w + 2 * (size_t)big); am.t_off = w + 3 * (size_t)big;
-            am.nonempty = w + 4 * (size_t)big; am.invalid = w + 4 * (size_t)big + 64 * (size_t)big;
-            am.cursor = w + (size_t)big * (4 + 128);
-            am.c2 = c->absm_c2 + C2_SLACK; am.rspec = c->absm_rspec; am.sinfo = c->absm_sinfo; am.n_bases = b->n_bases; am.n_reads = n;
-            if (early) HIPCHK(hipStreamWaitEvent(st, c->absm_done, 0));
-            else HIPCHK(packed_fill(c->absm_rspec, 0, (size_t)n + 1, st));
-            am.need128 = c->absm_need; am.planes = c->absm_planes; am.ns = c->absm_ns; am.row_cap = (uint32_t)rows;
-            am.bests = c->mid_bests; am.tpl = -1; am.den = 0; am.kit_slot = -1;
-            // issue priority of the row loops rotated every two rows by workgroup parity (abs_setprio; two waves of different
-            // launches share a SIMD): 4.79 against 4.91 ms per step at 1 M reads (tools/r04_absmid_prio.sh); QCAT_HIP_MIDDLE_ABS_PRIO
-            const QOptVal pr = opt_is_set(QO_MIDDLE_ABS_PRIO) ? qopt_get(QO_MIDDLE_ABS_PRIO) : qopt_get(QO_ABS_PRIO);
-            am.prio = pr ? atoi(pr) : 2;
-            am.r1_scalar = hk.r1_scalar;
-            HIPCHK(packed_fill(am.cursor, 0, MAX_T * 4, st));
-            HIPCHK(packed_fill_flush(st));
-            // the M-ends' first windows (k_mid_windows) come from the packed batch too: QCAT_HIP_MIDDLE_ABS_WINDOWS=0: from the reads, beside
-            const bool c2win = mid_bs && !((opt_is_set(QO_MIDDLE_ABS_WINDOWS) && opt_val(QO_MIDDLE_ABS_WINDOWS, 0) == 0));
-            fork_join(sc, st, (mid_bs && !c2win) ? 2 : 1, [&](int i, hipStream_t q) {
-                if (i == 0) qcat_absmid_prepare(q, &am, c2win ? c->mid_win2 : nullptr, c2win ? c->mid_wspec : nullptr, early ? 2 : 3); else launch_mid_windows(q);
-            });
-            use_absm = true;
-            c->absm_last_big = big; c->absm_last_128 = tiles;
-        }
-    }
-    HIPCHK(packed_fill_flush(st));                                 // (no bit-sliced interior scan: the job tables' fills leave here)
-    int absm_side = 0;                                             // templates on the bit-sliced path: launches side by side
-    if (use_absm) for (int t = 0; t < hk.nt; ++t) if ((am.kit_mask >> hk.tpl[t].kit_slot) & 1u) ++absm_side;
-    if (mid_bs && !use_absm) launch_mid_windows(st);
-    fork_join(sc, st, hk.nt, [&](int t, hipStream_t q) {
-        if (use_absm && ((am.kit_mask >> hk.tpl[t].kit_slot) & 1u)) {
-            AbsMidArgs at = am;
-            at.bests = c->mid_bests + (size_t)t * slots; at.tpl = t; at.den = hk.tpl[t].den; at.kit_slot = hk.tpl[t].kit_slot;
-            at.cursor = am.cursor + t;
-            // persistent two-wave workgroups: four per CU (two waves per SIMD) shared by the templates that run side by side --
-            // two launches of four per CU each do not fit the register file together, and the second one then runs after
-            // the first (1.2 + 0.6 ms at 1 M reads against ~1.0 ms side by side).  QCAT_HIP_MIDDLE_ABS_WGS=<per CU and launch>
-            // A template of up to 46 columns walks a tile on ONE wave (k_adapter_mid1: eight per CU); QCAT_HIP_MIDDLE_ABS_ONE_WAVE=0 / 1: pipeline / one wave whatever the size.
-            const QOptVal wg = qopt_get(QO_MIDDLE_ABS_WGS);
-            const QOptVal ow = qopt_get(QO_MIDDLE_ABS_ONE_WAVE);
-            const int sk = hk.tpl[t].static_kernel;
-            // one wave per tile from 2.75 big tiles per CU (720 k reads): with fewer tiles than wave slots a tile's walk is the kernel,
-            // and the pipeline's two waves halve it (400 k reads: interior phase 1.95 against 2.29 ms; 800 k: 2.96 against 2.87)
-            const bool big_enough = slots >= (size_t)abs_cu_count() * 2048 * 11 / 4;
-            const bool one = (ow ? atoi(ow) != 0 : big_enough) && qcat_absmid_launch(sk, 1, 0, nullptr, nullptr) != 0;
-            const int per_cu = wg ? atoi(wg) : std::max(1, (one ? 8 : 4) / std::max(1, absm_side));
-            const unsigned grid = (unsigned)std::min<uint32_t>(am.n_tiles, (uint32_t)(abs_cu_count() * per_cu));
-            (void)qcat_absmid_launch(sk, one ? 1 : 2, grid, q, &at);
-        }
-        MiddleAdapterArgs ma{kp, b->bases, b->offsets, c->mid_sorted, c->mid_len, c->mid_tables,
-                             c->mid_bests + (size_t)t * slots, t, use_absm ? c->absm_need : nullptr};
-        launch_adapter_middle(hk.tpl[t].static_kernel, dim3(tiles), q, ma);
-    });
-    {
-        const uint32_t fblocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, 2048);
-        hipLaunchKernelGGL(k_adapter_finish, dim3(fblocks), dim3(256), 0, st, kp.kit, c->mid_len, (uint32_t)slots,
-                           c->mid_bests, hk.nt, c->mid_recs, sc->jt, (const int32_t*)c->mid_fallback, -1, (const uint8_t*)sc->wspec, sc->jobinfo, (int2*)nullptr, (uint32_t*)nullptr);
-    }
-    const int nsets = hk.mode == QCAT_MODE_DUAL ? 2 : 1;
-    rc = packed_barcode(st, kp, hk, (uint32_t)slots, c->mid_recs, sc, [&](uint32_t max_tiles, const BsPlan* taken, hipStream_t gq) {
-        const uint64_t gthreads = (uint64_t)max_tiles * 64 * (WIN_STRIDE / 16);
-        hipLaunchKernelGGL(k_mid_gather, dim3((uint32_t)((gthreads + 255) / 256)), dim3(256), 0, gq,
-                           b->bases, b->offsets, hk.max_align, c->mid_sorted, c->mid_recs, sc->sorted, sc->jt, nsets,
-                           sc->tilebuf, sc->tmeta, taken);
-    }, (int16_t*)nullptr, 0u, [](const char*) {});
-    if (!rc) rc = jit_take_error();
-    if (rc) return set_err(rc, packed_last_error());
-    hipLaunchKernelGGL(k_mid_finalize, dim3((n + 255) / 256), dim3(256), 0, st, kp.kit, c->mid_recs, c->mid_slot, n, c->results, c->mid_generic);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// barcodes of the kit's largest set (at least 1): the stride of the one-wave kernels' score arrays
-static int max_set_barcodes(const DevKit& hk) {
-    int maxb = 1;
+// barcodes of the kit's largest set; at least 1 as the stride of the one-wave kernels' score arrays
+static int max_set_barcodes(const DevKit& hk, int at_least = 1) {
+    int maxb = at_least;
     for (int t = 0; t < hk.nt; ++t) for (int s = 0; s < 2; ++s) maxb = std::max(maxb, (int)hk.tpl[t].sets[s].n);
     return maxb;
 }
@@ -934,9 +680,200 @@ static int simple_packed_scan(qcat_ctx* c, KitPtrs kp, const DevKit& hk, size_t 
     return 0;
 }
 
-// core: scan a resident batch.  dbg: optional debug buffers sized by the caller.
-static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, bool debug, uint32_t row_stride,
-                              bool adapter_only = false, int resume_kit_mask = -1, bool keep_counts = false) {
+// the kind of pass a scan of a resident batch is: plain, a debug scan, the vote pass of kit auto or its resumed second pass;
+// a later chunk of a pipelined call keeps the count vector
+struct ScanPass {
+    bool debug_scan = false;            // every end's template scores into dbg_tpl and -- row_stride > 0 -- every barcode's raw score into dbg_rows
+    uint32_t row_stride = 0;
+    bool adapter_only = false;          // the adapter templates of every kit only: the records the vote reads, no results
+    int resume_kit_mask = -1;           // >= 0: the adapter alignments of the vote pass are still on the device; their merge for these kit
+                                        // slots (RESUME_KIT_ON_DEVICE: the slot k_pick_kit chose), the barcode phase and the finalisation
+    bool keep_counts = false;           // the count vector goes on from the scan before
+    static ScanPass plain() { return ScanPass{}; }
+    static ScanPass debug(uint32_t row_stride) { ScanPass p; p.debug_scan = true; p.row_stride = row_stride; return p; }
+    static ScanPass vote() { ScanPass p; p.adapter_only = true; return p; }
+    static ScanPass resume(int kit_mask) { ScanPass p; p.resume_kit_mask = kit_mask; return p; }
+    ScanPass keeping_counts(bool keep = true) const { ScanPass p = *this; p.keep_counts = keep; return p; }
+    bool resumed() const { return resume_kit_mask >= 0; }
+};
+
+// the kernels a scan takes, decided once from the kit, the batch size, the pass and the options (nothing here touches the
+// context's state or the stream)
+struct ScanPath {
+    bool packed_kit;                    // the kit fits the packed kernels
+    bool use_packed;                    // ... and the read ends of this batch take them (not the handful-of-reads path)
+    bool packed_pairs;                  // ... through packed_scan -- adapter templates and barcode sets, not simple mode: job tables, lazy windows, slim results
+    bool tiny; int tiny_maxb;           // one wave per alignment (kernels_tiny.inc); the stride of its score arrays
+    bool lazy;                          // byte windows for the flagged ends only
+    bool slim;                          // packed barcode results instead of the records
+    bool abs_planes;                    // a scan from the reads whose adapter phase runs bit-sliced: flag block and letter planes ahead of it
+    bool fused_front;                   // ... its windows and planes from one kernel (k_pack_planes)
+    bool middle_packed;                 // the interiors of --detect-middle on the packed kernels (middle_host.inc)
+};
+
+static ScanPath scan_choose_path(bool force_generic, const DevKit& hk, size_t n_ends, const ScanPass& pass) {
+    ScanPath p{};
+    p.packed_kit = hk.fast_ok && !force_generic && packed_supported(hk);
+    // a handful of read ends (detect_barcode on one read, a few reads of a test): one wave per alignment, kernels_tiny.inc
+    // (QCAT_HIP_TINY_MAX_ENDS: the largest batch that goes there, 0: none; QCAT_HIP_NO_TINY=1)
+    // the path pays while its waves -- one per (read end, template) plus one per (read end, set, barcode) -- fit the chip a few
+    // times over: up to TINY_MAX_WAVES of them (tools/tiny_crossover.py: PBC096 wins to ~180 reads, NBD104 to ~700)
+    const QOptVal tiny_env = qopt_get(QO_TINY_MAX_ENDS);
+    p.tiny_maxb = max_set_barcodes(hk);
+    const uint64_t tiny_waves = n_ends * (uint64_t)(hk.nt + p.tiny_maxb * (hk.mode == QCAT_MODE_DUAL ? 2 : 1));
+    const bool tiny_fits = tiny_env ? n_ends <= (uint64_t)std::max<long long>(0, atoll(tiny_env)) : tiny_waves <= (uint64_t)TINY_MAX_WAVES;
+    p.tiny = n_ends > 0 && n_ends <= 4096 && tiny_fits && !opt_on(QO_NO_TINY) && hk.mode != QCAT_MODE_SIMPLE && !pass.resumed() &&
+             !pass.adapter_only && !force_generic && hk.gap_open == hk.gap_extend;
+    p.use_packed = p.packed_kit && !p.tiny;        // (no job tables, no lazy windows: the tiny kernels read byte windows)
+    p.packed_pairs = p.use_packed && hk.mode != QCAT_MODE_SIMPLE;
+    // lazy byte windows (round 4): a kit whose every template runs a generated kernel reads plain windows at two
+    // bits per code everywhere (dev_window16), so the byte windows -- 3.3 of the pack kernel's 4.1 GB of stores per
+    // 10 M reads -- are written for the flagged ends only (k_expand_special; QCAT_HIP_EAGER_BYTES=1: all of them)
+    p.lazy = p.packed_pairs && hk.adapter_f16 && !opt_on(QO_NO_STATIC) && !opt_on(QO_NO_STATIC_ADAPTER) && !opt_on(QO_EAGER_BYTES);
+    for (int t = 0; t < hk.nt && p.lazy; ++t) p.lazy = hk.tpl[t].static_kernel >= 0;
+    // packed barcode results (kernels_bitslice.inc: k_bs_select_ordered) instead of 8 bytes scattered into every record;
+    // debug scans keep the records complete for the traces
+    p.slim = p.packed_pairs && !pass.debug_scan && !opt_on(QO_NO_SLIM);
+    // a batch the bit-sliced adapter kernels will take: its windows and their letter planes in one pass (kernels_abs.inc:
+    // k_pack_planes), so that the windows are not read back from memory.  QCAT_HIP_PACK_PLANES=0 (A/B builds):
+    // k_pack_windows here and k_abs_planes in the adapter phase, the route of every other batch and of the vote pass of kit auto
+    p.abs_planes = p.packed_pairs && !pass.resumed() && packed_abs_wanted(hk, (uint32_t)n_ends, true);
+    p.fused_front = p.abs_planes && !pass.adapter_only && opt_val(QO_PACK_PLANES, 1) != 0;
+    p.middle_packed = hk.scan_middle && !pass.adapter_only && p.packed_kit && middle_packed_ok(hk);
+    return p;
+}
+
+// step 1, size the buffers: room for n reads / n_ends read ends in the context's scan buffers; a debug scan's buffers start cleared
+static int scan_size_buffers(qcat_ctx* c, const DevKit& hk, uint32_t n, size_t n_ends, const ScanPass& pass) {
+    int rc;
+    if ((rc = grow(c->win, n_ends * WIN_STRIDE + 512))) return rc;    // + slack: k_job_gather reads whole dwords, k_bs_barcode 84 bytes from any region start
+    if ((rc = grow(c->wlen, n_ends))) return rc;
+    if ((rc = grow(c->wspec, n_ends))) return rc;
+    // + slack: readers take whole dwords past a region's end -- and, round 5, one dword in FRONT of the first window (a front-padded
+    // unit of the bit-sliced barcode kernels fetches from up to BS_PAD_ROWS bases before a region): the windows start WIN2_FRONT words in
+    if ((rc = grow(c->win2, n_ends * WIN2_WORDS + 64 + WIN2_FRONT))) return rc;
+    if ((rc = grow(c->recs, n_ends))) return rc;
+    if ((rc = grow(c->results, (size_t)n))) return rc;
+    if ((rc = grow(c->counts, (size_t)hk.n_buckets))) return rc;
+    if (pass.debug_scan) {
+        const uint32_t row_stride = pass.row_stride;
+        if ((rc = grow(c->dbg_tpl, n_ends * 2 * MAX_T))) return rc;
+        if (row_stride && (rc = grow(c->dbg_rows, n_ends * 2 * row_stride))) return rc;
+        HIPCHK(hipMemsetAsync(c->dbg_tpl, 0, n_ends * 2 * MAX_T * 4, c->stream));
+        if (row_stride) HIPCHK(hipMemsetD16Async((hipDeviceptr_t)c->dbg_rows, (unsigned short)0x8000, n_ends * 2 * row_stride, c->stream));
+    }
+    return 0;
+}
+
+// step 3, the front end of a scan that starts from the reads: letter flags, windows at one byte and at two bits per code.
+// With the job tables and the adapter tile flags sized here instead of after the pack kernel, their fills leave with the
+// count vector's and the letter flags' as ONE launch in front of it (the caller's FillScope)
+static int scan_front_end(qcat_ctx* c, const DevKit& hk, const qcat_batch* b, int ends, size_t n_ends, const ScanPath& path) {
+    int rc;
+    const uint32_t n = b->n_reads;
+    HIPCHK(packed_fill(c->wspec, 0, n_ends, c->stream));
+    c->packed.abs_ready = 0;
+    if (g_fill_defer && path.packed_pairs) {
+        if ((rc = packed_prepare(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());     // (sizes the slim buffers)
+        c->packed.prepared = true;
+        if (path.abs_planes && (rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
+    }
+    HIPCHK(packed_fill_flush(c->stream));
+    c->win2_valid = true;
+    c->packed.lazy = path.lazy;
+    const int lazy_bytes = path.lazy ? 1 : 0;
+    if (path.fused_front) {
+        if (c->packed.abs_zeroed != (uint32_t)n_ends && (rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
+        const uint32_t tiles = ((uint32_t)n_ends + ABS_TILE - 1) / ABS_TILE;
+        uint32_t* cursor = reinterpret_cast<uint32_t*>(c->packed.abs_flags.get());
+        uint32_t* tile_any = cursor + MAX_T;
+        (void)qcat_abs_launch_pack_planes(c->stream, b->bases, b->offsets, n, ends, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy_bytes,
+                                          c->packed.abs_planes, c->packed.abs_valid, reinterpret_cast<uint8_t*>(tile_any + tiles), tile_any);
+        c->packed.abs_ready = (uint32_t)n_ends;
+        c->last_fused_ends = (uint32_t)n_ends;
+    } else {
+        const uint32_t pack_blocks = (uint32_t)((n_ends + PACK_WINDOWS - 1) / PACK_WINDOWS);
+        if (ends == 2) hipLaunchKernelGGL(k_pack_windows<2>, dim3(pack_blocks), dim3(PACK_THREADS), 0, c->stream,
+                                          b->bases, b->offsets, n, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy_bytes);
+        else hipLaunchKernelGGL(k_pack_windows<1>, dim3(pack_blocks), dim3(PACK_THREADS), 0, c->stream,
+                                b->bases, b->offsets, n, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy_bytes);
+    }
+    if (path.lazy) hipLaunchKernelGGL(k_expand_special, dim3((uint32_t)((n_ends + 255) / 256)), dim3(256), 0, c->stream,
+                                      b->bases, b->offsets, n, ends, hk.max_align, c->wspec, c->win);
+    mark(c, "k_pack_windows");
+    return 0;
+}
+
+// step 4, the scan of the read ends: simple mode on the packed end-tracking kernels or on the general one, else the packed
+// path, the one-wave kernels or the general kernel
+static int scan_read_ends(qcat_ctx* c, const qcat_kit* kit, KitPtrs kp, size_t n_ends, const ScanPass& pass, const ScanPath& path) {
+    const DevKit& hk = kit->hk.dk;
+    int32_t* dbg_tpl = pass.debug_scan ? c->dbg_tpl.get() : nullptr;
+    int16_t* dbg_rows = pass.debug_scan && pass.row_stride ? c->dbg_rows.get() : nullptr;
+    const uint32_t row_stride = pass.row_stride;
+    int rc;
+    if (hk.mode == QCAT_MODE_SIMPLE && kit->hk.simple_packed && !c->force_generic && !opt_on(QO_NO_SIMPLE_PACKED)) {
+        // every batch size from one read end up: a chunked packed scan beats one lane walking the whole list
+        if ((rc = simple_packed_scan(c, kp, hk, n_ends, dbg_rows, row_stride))) return rc;
+        mark(c, "k_simple_packed");
+    } else if (hk.mode == QCAT_MODE_SIMPLE) {
+        uint32_t blocks = (uint32_t)((n_ends + GEN_THREADS - 1) / GEN_THREADS);
+        hipLaunchKernelGGL(k_scan_simple, dim3(blocks), dim3(GEN_THREADS), 0, c->stream, kp, c->win, c->wlen, (uint32_t)n_ends, c->recs,
+                           dbg_rows, row_stride);
+        mark(c, "k_scan_simple");
+    } else if (path.use_packed) {
+        rc = packed_scan(c->stream, kp, hk, c->win, c->wlen, (uint32_t)n_ends, c->recs, &c->packed, dbg_tpl, dbg_rows, row_stride,
+                         [&](const char* nm) { mark(c, nm); }, pass.adapter_only, pass.resume_kit_mask);
+        if (rc) return set_err(rc, packed_last_error());
+    } else if (path.tiny) {
+        TinyArgs ta{kp, c->win, c->wlen, nullptr, nullptr, (uint32_t)n_ends, c->recs, c->tiny_tpl, c->tiny_sc, (uint32_t)path.tiny_maxb,
+                    dbg_tpl, dbg_rows, row_stride, 0};
+        hipLaunchKernelGGL(k_tiny_adapter, dim3((uint32_t)n_ends * (uint32_t)hk.nt), dim3(64), 0, c->stream, ta);
+        hipLaunchKernelGGL(k_tiny_decide, dim3((uint32_t)((n_ends + 63) / 64)), dim3(64), 0, c->stream, ta);
+        hipLaunchKernelGGL(k_tiny_barcode, dim3((uint32_t)path.tiny_maxb, (uint32_t)n_ends * 2), dim3(64), 0, c->stream, ta);
+        hipLaunchKernelGGL(k_tiny_select, dim3((uint32_t)n_ends * 2), dim3(64), 0, c->stream, ta);
+        mark(c, "k_scan_tiny");
+    } else {
+        uint32_t blocks = (uint32_t)((n_ends + GEN_THREADS - 1) / GEN_THREADS);
+        hipLaunchKernelGGL(k_scan_generic, dim3(blocks), dim3(GEN_THREADS), 0, c->stream,
+                           kp, c->win, c->wlen, (uint32_t)n_ends, c->recs, dbg_tpl, dbg_rows, row_stride, pass.adapter_only ? 1 : 0);
+        mark(c, "k_scan_generic");
+    }
+    return 0;
+}
+
+// step 5, finalise (every pass but the vote): the records of the reads and their counts; --detect-middle kits scan the
+// interiors of the called reads in between (middle_host.inc, k_scan_middle for what that leaves) and count afterwards
+static int scan_finalize(qcat_ctx* c, const DevKit& hk, KitPtrs kp, const qcat_batch* b, const ScanPath& path) {
+    const uint32_t n = b->n_reads;
+    // every block zeroes and flushes an LDS histogram of n_buckets entries with global atomics on the same few counters:
+    // fewer, fatter blocks -- 1024 (measured, tools/r04_fin.sh: config 2 0.059 -> 0.028 ms against 4096 blocks, config 3
+    // 0.235 -> 0.207 ms), 512 when the bucket vector is long (dual kits: 0.052 against 0.072 ms)
+    const QOptVal fb_env = qopt_get(QO_FIN_BLOCKS);                          // (A/B runs)
+    uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, fb_env ? (uint64_t)std::max(1, atoi(fb_env)) : (hk.n_buckets > 2048 ? 512 : 1024));
+    const bool middle = hk.scan_middle != 0;
+    hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(256), fin_lds_bytes(hk.n_buckets, !middle), c->stream,
+                       kp, c->recs, b->offsets, b->true_len, n, c->results, middle ? nullptr : c->counts,
+                       path.slim ? c->packed.bcres : nullptr, path.slim ? c->packed.fin : nullptr);
+    mark(c, "k_finalize");
+    if (!middle) return 0;
+    int rc;
+    const uint8_t* only = nullptr;
+    if (path.middle_packed) {                              // (also after the tiny kernels: the interiors are no handful of cells)
+        if ((rc = middle_packed(c->stream, &c->middle, &c->packed, kp, hk, b, n, c->results, c->win))) return rc;
+        only = c->middle.mid_generic;                      // interiors beyond the packed path's length classes
+        mark(c, "k_middle_packed");
+    }
+    if ((rc = middle_wave_leftovers(c->stream, &c->middle, kp, hk, b, n, c->results, path.tiny_maxb, only && !c->force_generic))) return rc;
+    hipLaunchKernelGGL(k_scan_middle, dim3((n + GEN_THREADS - 1) / GEN_THREADS), dim3(GEN_THREADS), 0, c->stream,
+                       kp, b->bases, b->offsets, n, c->results, only);
+    hipLaunchKernelGGL(k_count, dim3(blocks), dim3(256), 0, c->stream, kp, c->results, b->offsets, b->true_len, n, c->counts);
+    mark(c, "k_scan_middle");
+    return 0;
+}
+
+// core: scan a resident batch
+static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, const ScanPass& pass) {
     if (!c || !kit || !b) return set_err(QCAT_ERR_ARG, "null argument");
     if (b->device != c->device) return set_err(QCAT_ERR_ARG, "batch lives on another device than the context");
     HIPCHK(hipSetDevice(c->device));
@@ -949,192 +886,51 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, b
     const size_t n_ends = (size_t)n * ends;
     if (n_ends >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "batch too large (>= 2^31 read ends)");
 
-    if ((rc = grow(c->win, n_ends * WIN_STRIDE + 512))) return rc;    // + slack: k_job_gather reads whole dwords, k_bs_barcode 84 bytes from any region start
-    if ((rc = grow(c->wlen, n_ends))) return rc;
-    if ((rc = grow(c->wspec, n_ends))) return rc;
-    // + slack: readers take whole dwords past a region's end -- and, round 5, one dword in FRONT of the first window (a front-padded
-    // unit of the bit-sliced barcode kernels fetches from up to BS_PAD_ROWS bases before a region): the windows start WIN2_FRONT words in
-    if ((rc = grow(c->win2, n_ends * WIN2_WORDS + 64 + WIN2_FRONT))) return rc;
-    if ((rc = grow(c->recs, n_ends))) return rc;
-    if ((rc = grow(c->results, (size_t)n))) return rc;
-    if ((rc = grow(c->counts, (size_t)hk.n_buckets))) return rc;
-    if (debug) {
-        if ((rc = grow(c->dbg_tpl, n_ends * 2 * MAX_T))) return rc;
-        if (row_stride && (rc = grow(c->dbg_rows, n_ends * 2 * row_stride))) return rc;
-        HIPCHK(hipMemsetAsync(c->dbg_tpl, 0, n_ends * 2 * MAX_T * 4, c->stream));
-        if (row_stride) HIPCHK(hipMemsetD16Async((hipDeviceptr_t)c->dbg_rows, (unsigned short)0x8000, n_ends * 2 * row_stride, c->stream));
-    }
+    // 1. size the buffers, 2. choose the path
+    if ((rc = scan_size_buffers(c, hk, n, n_ends, pass))) return rc;
     c->last_n_reads = n;
     c->last_buckets = hk.n_buckets;
-    c->last_kit = adapter_only ? nullptr : kit;
+    c->last_kit = pass.adapter_only ? nullptr : kit;
     timing_slot(c);
-    // the fills of a scan leave as ONE launch in front of the pack kernel (k_fill_multi): count vector, letter flags, and --
-    // with the job tables and the adapter tile flags sized here instead of after the pack kernel -- theirs too
-    const bool packed_kit = hk.fast_ok && !c->force_generic && packed_supported(hk);
-    bool use_packed = packed_kit;
-    // a handful of read ends (detect_barcode on one read, a few reads of a test): one wave per alignment, kernels_tiny.inc
-    // (QCAT_HIP_TINY_MAX_ENDS: the largest batch that goes there, 0: none; QCAT_HIP_NO_TINY=1)
-    // the path pays while its waves -- one per (read end, template) plus one per (read end, set, barcode) -- fit the chip a few
-    // times over: up to TINY_MAX_WAVES of them (tools/tiny_crossover.py: PBC096 wins to ~180 reads, NBD104 to ~700)
-    const QOptVal tiny_env = qopt_get(QO_TINY_MAX_ENDS);
-    const int tiny_maxb = max_set_barcodes(hk);
-    const uint64_t tiny_waves = n_ends * (uint64_t)(hk.nt + tiny_maxb * (hk.mode == QCAT_MODE_DUAL ? 2 : 1));
-    const bool tiny_fits = tiny_env ? n_ends <= (uint64_t)std::max<long long>(0, atoll(tiny_env)) : tiny_waves <= (uint64_t)TINY_MAX_WAVES;
-    const bool tiny = n_ends > 0 && n_ends <= 4096 && tiny_fits && !opt_on(QO_NO_TINY) && hk.mode != QCAT_MODE_SIMPLE && resume_kit_mask < 0 &&
-                      !adapter_only && !c->force_generic && hk.gap_open == hk.gap_extend;
-    c->last_tiny_ends = tiny ? (uint32_t)n_ends : 0;
+    const ScanPath path = scan_choose_path(c->force_generic != 0, hk, n_ends, pass);
+    c->last_tiny_ends = path.tiny ? (uint32_t)n_ends : 0;
     c->last_fused_ends = 0;
-    if (tiny) {
-        if ((rc = tiny_buffers(c, (size_t)n_ends, tiny_maxb))) return rc;
-        use_packed = false;                        // (no job tables, no lazy windows: the tiny kernels read byte windows)
-    }
+    if (path.tiny && (rc = tiny_buffers(c, n_ends, path.tiny_maxb))) return rc;
+
+    // the fills of a scan leave as ONE launch in front of the pack kernel (k_fill_multi): the count vector's here, the front end's
     FillScope fills(n != 0 && !opt_on(QO_NO_FILL_MERGE));      // (every return before a flush drops what was queued)
-    if (!keep_counts) HIPCHK(packed_fill(c->counts, 0, (size_t)hk.n_buckets * 8, c->stream));
+    if (!pass.keep_counts) HIPCHK(packed_fill(c->counts, 0, (size_t)hk.n_buckets * 8, c->stream));
     if (n == 0) { HIPCHK(packed_fill_flush(c->stream)); return 0; }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[0], c->stream));   // (an empty batch returned above: its slot holds no marks)
-    c->absm_codes_early = false;
-    if (hk.scan_middle && !adapter_only && packed_kit && middle_packed_ok(hk) && (rc = absmid_codes_early(c, hk, b, n))) return rc;
+    c->middle.absm_codes_early = false;
+    if (path.middle_packed && (rc = absmid_codes_early(c->stream, &c->middle, hk, b, n))) return rc;
 
     KitPtrs kp{kd->kit, kd->codes, kd->ids, kd->tables};
     g_jit = kd;
     c->packed.prepared = false; c->packed.abs_zeroed = 0; c->packed.redo_zeroed = false;
-    if (resume_kit_mask < 0) {
-        HIPCHK(packed_fill(c->wspec, 0, n_ends, c->stream));
-        c->packed.abs_ready = 0;
-        if (g_fill_defer && use_packed && hk.mode != QCAT_MODE_SIMPLE) {
-            c->packed.slim = use_packed && !debug && !opt_on(QO_NO_SLIM);     // (packed_prepare sizes the slim buffers)
-            if ((rc = packed_prepare(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
-            c->packed.prepared = true;
-            if (packed_abs_wanted(hk, (uint32_t)n_ends, true) &&
-                (rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
-        }
-        HIPCHK(packed_fill_flush(c->stream));
-        c->win2_valid = true;
-        // lazy byte windows (round 4): a kit whose every template runs a generated kernel reads plain windows at two
-        // bits per code everywhere (dev_window16), so the byte windows -- 3.3 of the pack kernel's 4.1 GB of stores per
-        // 10 M reads -- are written for the flagged ends only (k_expand_special; QCAT_HIP_EAGER_BYTES=1: all of them)
-        bool lazy = use_packed && hk.mode != QCAT_MODE_SIMPLE && hk.adapter_f16 && !opt_on(QO_NO_STATIC) &&
-                    !opt_on(QO_NO_STATIC_ADAPTER) && !opt_on(QO_EAGER_BYTES);
-        for (int t = 0; t < hk.nt && lazy; ++t) lazy = hk.tpl[t].static_kernel >= 0;
-        c->packed.lazy = lazy;
-        // a batch the bit-sliced adapter kernels will take: its windows and their letter planes in one pass (kernels_abs.inc:
-        // k_pack_planes), so that the windows are not read back from memory.  QCAT_HIP_PACK_PLANES=0 (A/B builds):
-        // k_pack_windows here and k_abs_planes in the adapter phase, the route of every other batch and of the vote pass of kit auto
-        if (use_packed && hk.mode != QCAT_MODE_SIMPLE && !adapter_only && opt_val(QO_PACK_PLANES, 1) != 0 && packed_abs_wanted(hk, (uint32_t)n_ends, true)) {
-            if (c->packed.abs_zeroed != (uint32_t)n_ends && (rc = packed_abs_buffers(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
-            const uint32_t tiles = ((uint32_t)n_ends + ABS_TILE - 1) / ABS_TILE;
-            uint32_t* cursor = reinterpret_cast<uint32_t*>(c->packed.abs_flags.get());
-            uint32_t* tile_any = cursor + MAX_T;
-            (void)qcat_abs_launch_pack_planes(c->stream, b->bases, b->offsets, n, ends, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0,
-                                              c->packed.abs_planes, c->packed.abs_valid, reinterpret_cast<uint8_t*>(tile_any + tiles), tile_any);
-            c->packed.abs_ready = (uint32_t)n_ends;
-            c->last_fused_ends = (uint32_t)n_ends;
-        } else {
-            const uint32_t pack_blocks = (uint32_t)((n_ends + PACK_WINDOWS - 1) / PACK_WINDOWS);
-            if (ends == 2) hipLaunchKernelGGL(k_pack_windows<2>, dim3(pack_blocks), dim3(PACK_THREADS), 0, c->stream,
-                                              b->bases, b->offsets, n, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0);
-            else hipLaunchKernelGGL(k_pack_windows<1>, dim3(pack_blocks), dim3(PACK_THREADS), 0, c->stream,
-                                    b->bases, b->offsets, n, hk.max_align, c->win, c->wlen, c->wspec, c->win2 + WIN2_FRONT, lazy ? 1 : 0);
-        }
-        if (lazy) hipLaunchKernelGGL(k_expand_special, dim3((uint32_t)((n_ends + 255) / 256)), dim3(256), 0, c->stream,
-                                     b->bases, b->offsets, n, ends, hk.max_align, c->wspec, c->win);
-        mark(c, "k_pack_windows");
-    }
-    if (resume_kit_mask >= 0 && g_fill_defer && use_packed && c->packed.slices_single && hk.mode != QCAT_MODE_SIMPLE) {
-        // (a resumed scan -- the second pass of a kit-auto batch: its job tables' fills with the count vector's, one launch)
-        c->packed.slim = use_packed && !debug && !opt_on(QO_NO_SLIM);
+    c->packed.slim = path.slim;
+    // 3. front end -- or, a resumed scan (the second pass of a kit-auto batch): its job tables' fills with the count vector's, one launch
+    if (!pass.resumed()) {
+        if ((rc = scan_front_end(c, hk, b, ends, n_ends, path))) return rc;
+    } else if (g_fill_defer && path.packed_pairs && c->packed.slices_single) {
         if ((rc = packed_prepare(c->stream, hk, (uint32_t)n_ends, &c->packed))) return set_err(rc, packed_last_error());
         c->packed.prepared = true;
     }
     HIPCHK(packed_fill_flush(c->stream));               // (a resumed scan: the count vector's fill)
-    if (hk.mode == QCAT_MODE_SIMPLE && adapter_only) return set_err(QCAT_ERR_ARG, "simple mode has no adapter templates to vote with");
-    if (resume_kit_mask >= 0 && !(use_packed && c->packed.slices_single))
+    if (hk.mode == QCAT_MODE_SIMPLE && pass.adapter_only) return set_err(QCAT_ERR_ARG, "simple mode has no adapter templates to vote with");
+    if (pass.resumed() && !(path.use_packed && c->packed.slices_single))
         return set_err(QCAT_ERR_UNSUPPORTED, "the adapter pass of this kit cannot be resumed per kit (table or general kernels)");
     c->packed.wspec = c->wspec; c->packed.win = c->win; c->packed.win2 = c->win2_valid ? c->win2 + WIN2_FRONT : nullptr;
-    // packed barcode results (kernels_bitslice.inc: k_bs_select_ordered) instead of 8 bytes scattered into every record;
-    // debug scans keep the records complete for the traces
-    const bool slim = use_packed && !debug && hk.mode != QCAT_MODE_SIMPLE && !opt_on(QO_NO_SLIM);
-    c->packed.slim = slim;
-    if (hk.mode == QCAT_MODE_SIMPLE && kit->hk.simple_packed && !c->force_generic && !opt_on(QO_NO_SIMPLE_PACKED)) {
-        // every batch size from one read end up: a chunked packed scan beats one lane walking the whole list
-        if ((rc = simple_packed_scan(c, kp, hk, n_ends, (debug && row_stride) ? c->dbg_rows : nullptr, row_stride))) return rc;
-        mark(c, "k_simple_packed");
-    } else if (hk.mode == QCAT_MODE_SIMPLE) {
-        uint32_t blocks = (uint32_t)((n_ends + GEN_THREADS - 1) / GEN_THREADS);
-        hipLaunchKernelGGL(k_scan_simple, dim3(blocks), dim3(GEN_THREADS), 0, c->stream, kp, c->win, c->wlen, (uint32_t)n_ends, c->recs,
-                           (debug && row_stride) ? c->dbg_rows : nullptr, row_stride);
-        mark(c, "k_scan_simple");
-    } else if (use_packed) {
-        rc = packed_scan(c->stream, kp, hk, c->win, c->wlen, (uint32_t)n_ends, c->recs, &c->packed,
-                         debug ? c->dbg_tpl : nullptr, (debug && row_stride) ? c->dbg_rows : nullptr, row_stride,
-                         [&](const char* nm) { mark(c, nm); }, adapter_only, resume_kit_mask);
-        if (rc) return set_err(rc, packed_last_error());
-    } else if (tiny) {
-        TinyArgs ta{kp, c->win, c->wlen, nullptr, nullptr, (uint32_t)n_ends, c->recs, c->tiny_tpl, c->tiny_sc, (uint32_t)tiny_maxb,
-                    debug ? c->dbg_tpl : nullptr, (debug && row_stride) ? c->dbg_rows : nullptr, row_stride, 0};
-        hipLaunchKernelGGL(k_tiny_adapter, dim3((uint32_t)n_ends * (uint32_t)hk.nt), dim3(64), 0, c->stream, ta);
-        hipLaunchKernelGGL(k_tiny_decide, dim3((uint32_t)((n_ends + 63) / 64)), dim3(64), 0, c->stream, ta);
-        hipLaunchKernelGGL(k_tiny_barcode, dim3((uint32_t)tiny_maxb, (uint32_t)n_ends * 2), dim3(64), 0, c->stream, ta);
-        hipLaunchKernelGGL(k_tiny_select, dim3((uint32_t)n_ends * 2), dim3(64), 0, c->stream, ta);
-        mark(c, "k_scan_tiny");
-    } else {
-        uint32_t blocks = (uint32_t)((n_ends + GEN_THREADS - 1) / GEN_THREADS);
-        hipLaunchKernelGGL(k_scan_generic, dim3(blocks), dim3(GEN_THREADS), 0, c->stream,
-                           kp, c->win, c->wlen, (uint32_t)n_ends, c->recs,
-                           debug ? c->dbg_tpl : nullptr, (debug && row_stride) ? c->dbg_rows : nullptr, row_stride,
-                           adapter_only ? 1 : 0);
-        mark(c, "k_scan_generic");
-    }
-    if (!adapter_only) {
-        // every block zeroes and flushes an LDS histogram of n_buckets entries with global atomics on the same few counters:
-        // fewer, fatter blocks -- 1024 (measured, tools/r04_fin.sh: config 2 0.059 -> 0.028 ms against 4096 blocks, config 3
-        // 0.235 -> 0.207 ms), 512 when the bucket vector is long (dual kits: 0.052 against 0.072 ms)
-        const QOptVal fb_env = qopt_get(QO_FIN_BLOCKS);                          // (A/B runs)
-        uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, fb_env ? (uint64_t)std::max(1, atoi(fb_env)) : (hk.n_buckets > 2048 ? 512 : 1024));
-        const bool middle = hk.scan_middle != 0;
-        hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(256), fin_lds_bytes(hk.n_buckets, !middle), c->stream,
-                           kp, c->recs, b->offsets, b->true_len, n, c->results, middle ? nullptr : c->counts,
-                           (slim && !adapter_only) ? c->packed.bcres : nullptr, (slim && !adapter_only) ? c->packed.fin : nullptr);
-        mark(c, "k_finalize");
-        if (middle) {
-            const uint8_t* only = nullptr;
-            if (packed_kit && middle_packed_ok(hk)) {              // (also after the tiny kernels: the interiors are no handful of cells)
-                if ((rc = middle_packed(c, kp, hk, b, n))) return rc;
-                only = c->mid_generic;                  // interiors beyond the packed path's length classes
-                mark(c, "k_middle_packed");
-            }
-            // the reads the packed interior scan left (interiors of more than 16 384 letters ...): on one wave per alignment
-            // (kernels_tiny.inc: k_midw_*) up to MIDW_CAP of them per batch, the general kernel takes what is left after that
-            c->midw_ran = false;
-            if (only && hk.gap_open == hk.gap_extend && !opt_on(QO_NO_TINY) && !c->force_generic) {
-                constexpr uint32_t MIDW_CAP = 2048;
-                HIPCHK(c->midw_list.ensure(MIDW_CAP + 1));
-                HIPCHK(c->midw_tpl.ensure((size_t)MIDW_CAP * 2 * MAX_T * 2));
-                HIPCHK(c->midw_recs.ensure((size_t)MIDW_CAP * 2));
-                HIPCHK(c->midw_sc.ensure((size_t)MIDW_CAP * 2 * 2 * (size_t)tiny_maxb));
-                uint32_t* count = c->midw_list + MIDW_CAP;
-                HIPCHK(hipMemsetAsync(count, 0, sizeof(uint32_t), c->stream));
-                MidWaveArgs ma{kp, b->bases, b->offsets, n, c->results, c->mid_generic, c->midw_list, count, MIDW_CAP,
-                               c->midw_tpl, c->midw_recs, c->midw_sc, (uint32_t)tiny_maxb};
-                hipLaunchKernelGGL(k_midw_list, dim3((n + 255) / 256), dim3(256), 0, c->stream, ma);
-                hipLaunchKernelGGL(k_midw_adapter, dim3(1024), dim3(64), 0, c->stream, ma);
-                hipLaunchKernelGGL(k_midw_decide, dim3(MIDW_CAP * 2 / 64), dim3(64), 0, c->stream, ma);
-                hipLaunchKernelGGL(k_midw_barcode, dim3(4096), dim3(64), 0, c->stream, ma);
-                hipLaunchKernelGGL(k_midw_finish, dim3(MIDW_CAP / 64), dim3(64), 0, c->stream, ma);
-                c->midw_ran = true;
-            }
-            hipLaunchKernelGGL(k_scan_middle, dim3((n + GEN_THREADS - 1) / GEN_THREADS), dim3(GEN_THREADS), 0, c->stream,
-                               kp, b->bases, b->offsets, n, c->results, only);
-            hipLaunchKernelGGL(k_count, dim3(blocks), dim3(256), 0, c->stream, kp, c->results, b->offsets, b->true_len, n, c->counts);
-            mark(c, "k_scan_middle");
-        }
-    }
+
+    // 4. the read ends, 5. finalise
+    if ((rc = scan_read_ends(c, kit, kp, n_ends, pass, path))) return rc;
+    if (!pass.adapter_only && (rc = scan_finalize(c, hk, kp, b, path))) return rc;
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" int qcat_scan_resident(qcat_ctx* c, const qcat_kit* kit, const qcat_batch* b) {
-    return scan_resident_impl(c, const_cast<qcat_kit*>(kit), b, false, 0);
+    return scan_resident_impl(c, const_cast<qcat_kit*>(kit), b, ScanPass::plain());
 }
 
 extern "C" int qcat_ctx_synchronize(qcat_ctx* c) {
@@ -1206,12 +1002,7 @@ extern "C" int qcat_ctx_fused_front(const qcat_ctx* c, uint32_t* out) {
 // reads whose interior the latest --detect-middle scan put on the one-wave kernels (k_midw_*: interiors the packed interior scan
 // does not take); synchronises the stream; -1: null context, 0: none / the path did not run
 extern "C" int64_t qcat_ctx_middle_wave_reads(qcat_ctx* c) {
-    if (!c) return -1;
-    if (!c->midw_ran || !c->midw_list) return 0;
-    if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return -1;
-    uint32_t cnt = 0;
-    if (hipMemcpy(&cnt, c->midw_list + 2048, sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return (int64_t)std::min<uint32_t>(cnt, 2048u);
+    return c ? middle_wave_count(c->middle, c->device, c->stream) : -1;
 }
 extern "C" int64_t qcat_ctx_graph_replays(const qcat_ctx* c) { return c ? (int64_t)(c->api_graph.replays + c->scan_graph.replays) : -1; }
 // diagnostics of the latest scan of the read ends: super-tiles (2048 barcode alignments each) its bit-sliced barcode kernels took, per
@@ -1235,19 +1026,7 @@ extern "C" int qcat_ctx_barcode_bitslice_tiles(qcat_ctx* c, uint32_t* out) {
 // tiles in all, out[2] = tiles of 128 interiors left to the binary16 kernel, out[3] = tiles of 128 in all (all 0: path not taken)
 extern "C" int qcat_ctx_middle_bitslice_tiles(qcat_ctx* c, uint32_t* out) {
     if (!c || !out) return set_err(QCAT_ERR_ARG, "null argument");
-    out[0] = out[1] = out[2] = out[3] = 0;
-    if (!c->absm_last_big) return 0;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    std::vector<int32_t> rows(c->absm_last_big);
-    std::vector<uint8_t> need(c->absm_last_128);
-    HIPCHK(hipMemcpy(rows.data(), c->absm_tiles, rows.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(need.data(), c->absm_need, need.size(), hipMemcpyDeviceToHost));
-    for (int32_t r : rows) if (r > 0) ++out[0];
-    out[1] = c->absm_last_big;
-    for (uint8_t f : need) if (f) ++out[2];
-    out[3] = c->absm_last_128;
-    return 0;
+    return middle_bitslice_tiles(c->middle, c->device, c->stream, out);
 }
 extern "C" void* qcat_ctx_counts_devptr(qcat_ctx* c) { return c ? c->counts : nullptr; }
 extern "C" void* qcat_ctx_results_devptr(qcat_ctx* c) { return c ? c->results : nullptr; }
@@ -1926,7 +1705,7 @@ static int scan_batch_pipelined(qcat_ctx* c, qcat_kit* kit, const ReadView& rv,
         view.device = c->device; view.n_reads = nr; view.n_bases = total;
         view.bases_alloc = st.dev_bases_alloc; view.bases = st.dev_bases_alloc + BATCH_SLACK;
         view.offsets = st.dev_offsets; view.true_len = st.dev_len;
-        rc = scan_resident_impl(c, kit, &view, false, 0, false, -1, /*keep_counts=*/ci > 0);
+        rc = scan_resident_impl(c, kit, &view, ScanPass::plain().keeping_counts(ci > 0));
         if (rc) break;
         HIPCHK(hipMemcpyAsync(st.pin_results, c->results, (size_t)nr * sizeof(qcat_result), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipEventRecord(st.scanned, c->stream));
@@ -2019,12 +1798,8 @@ static int scan_debug_impl(qcat_ctx* c, const qcat_kit* ckit,
                            qcat_end_trace* traces, int16_t* bc_rows, uint32_t row_stride) {
     if (!c || !ckit || (!offsets && !ptrs) || !out) return set_err(QCAT_ERR_ARG, "null argument");
     qcat_kit* kit = const_cast<qcat_kit*>(ckit);
-    if (bc_rows) {
-        int need = 0;
-        for (int t = 0; t < kit->hk.dk.nt; ++t)
-            for (int s = 0; s < 2; ++s) need = std::max(need, kit->hk.dk.tpl[t].sets[s].n);
-        if ((int)row_stride < need) return set_err(QCAT_ERR_ARG, "row_stride smaller than the largest barcode set");
-    }
+    if (bc_rows && (int)row_stride < max_set_barcodes(kit->hk.dk, 0))
+        return set_err(QCAT_ERR_ARG, "row_stride smaller than the largest barcode set");
     qcat_batch* b = nullptr;
     int rc = batch_upload_windows(c, kit, bases, offsets, n_reads, &b, ptrs, lens);
     if (rc) return rc;
@@ -2036,10 +1811,10 @@ static int scan_debug_impl(qcat_ctx* c, const qcat_kit* ckit,
         // replay them as a graph, like the kit-auto calls (api_graph_run)
         KitOnDevice* kd = nullptr;
         rc = kit_on_device(kit, c->device, &kd);
-        if (!rc) rc = api_graph_run(c, c->scan_graph, kit, kd, b, 0, [&] { return scan_resident_impl(c, kit, b, false, 0); }, [] {});
+        if (!rc) rc = api_graph_run(c, c->scan_graph, kit, kd, b, 0, [&] { return scan_resident_impl(c, kit, b, ScanPass::plain()); }, [] {});
         else (void)hipStreamSynchronize(c->stream);
         if (!rc) { c->last_n_reads = n_reads; c->last_buckets = kit->hk.dk.n_buckets; }      // (a replay does not pass through scan_resident_impl)
-    } else rc = scan_resident_impl(c, kit, b, debug, bc_rows ? row_stride : 0);
+    } else rc = scan_resident_impl(c, kit, b, debug ? ScanPass::debug(bc_rows ? row_stride : 0) : ScanPass::plain());
     if (rc) (void)hipStreamSynchronize(c->stream);          // (the upload may still be reading the context's pinned staging)
     if (!rc) rc = fetch_back(c, out, n_reads, counts, kit->hk.dk.n_buckets);
     if (!rc && debug && n_reads) {
@@ -2076,7 +1851,7 @@ static int vote_buffer(qcat_ctx* c, size_t nb) {
 // adapter-only pass over a resident batch + k_vote: per-template votes / first voting read (host arrays of MAX_T)
 static int vote_resident(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, unsigned long long* hv, unsigned long long* hf) {
     for (int t = 0; t < MAX_T; ++t) { hv[t] = 0; hf[t] = ~0ull; }
-    int rc = scan_resident_impl(c, kit, b, false, 0, true);
+    int rc = scan_resident_impl(c, kit, b, ScanPass::vote());
     // (a failed step drains the stream before it returns: the caller's upload may still be reading the pinned staging)
     auto drained = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
     if (rc) return drained(rc);
@@ -2151,7 +1926,7 @@ static int scan_batch_auto_impl(qcat_ctx* c, const qcat_kit* ckit, const uint8_t
     // the device work of the call, in stream order behind the upload
     auto enqueue = [&]() -> int {
         // pass 1: every template of every kit against both ends (qcat/scanner_base.py:662-678)
-        int e = scan_resident_impl(c, kit, b, false, 0, true);
+        int e = scan_resident_impl(c, kit, b, ScanPass::vote());
         if (e) return e;
         {
             FillScope fills(true);
@@ -2175,7 +1950,7 @@ static int scan_batch_auto_impl(qcat_ctx* c, const qcat_kit* ckit, const uint8_t
             for (int t = 0; t < hk.nt; ++t) fprintf(stderr, " %llu/slot%d", dv[t], hk.tpl[t].kit_slot);
             fprintf(stderr, "\n");
         }
-        return scan_resident_impl(c, kit, b, false, 0, false, RESUME_KIT_ON_DEVICE);
+        return scan_resident_impl(c, kit, b, ScanPass::resume(RESUME_KIT_ON_DEVICE));
     };
     if ((rc = api_graph_run(c, c->api_graph, kit, kd, b, batch_reads, enqueue,
                             [&] { c->packed.kit_slot_dev = chosen_dev; c->packed.kit_slot_span = slot_span; }))) return rc;
