@@ -415,6 +415,36 @@ int  qcat_kit_partition_bins(const qcat_kit* kit);
  * Enqueues on the context's stream, synchronises once (the size of `out`).  The result is the same bytes run after run. */
 int  qcat_batch_partition(qcat_ctx* ctx, const qcat_kit* kit, const qcat_batch* batch,
                           const qcat_result* records, uint32_t flags, qcat_batch** out);
+/* ---- a read is more than its bases: the quality plane of a resident batch ----
+ * replaces, for reads that stay in HBM: the quality slice of the reference driver, cut together with the sequence in front of the
+ * length filter and the writers (qcat/cli.py:521-526, quality = quality[trim_5p:trim_3p]).
+ * qualities: one byte per base, read r at the same [offsets[r], offsets[r+1]) as its bases; opaque bytes.  No scan looks at the
+ * plane: qcat_scan_resident of a batch with qualities gives the records it gives without them.  qcat_batch_partition of a batch
+ * with qualities gives a batch with qualities: the kept slice of every read's plane at the output's offsets, moved in the same
+ * pass as the bases; bin_first and source are the same. */
+int  qcat_batch_upload_fastq(qcat_ctx* ctx, const uint8_t* bases, const uint8_t* qualities,
+                             const uint64_t* offsets, uint32_t n_reads, qcat_batch** out);
+/* 1 / 0; a negative status for a null batch */
+int  qcat_batch_has_qualities(const qcat_batch* batch);
+/* copy the quality plane back (n_bases bytes); a batch without a plane: QCAT_ERR_ARG */
+int  qcat_batch_download_qualities(qcat_ctx* ctx, const qcat_batch* batch, uint8_t* qualities);
+
+/* ---- resident batches from and as device pointers (replace nothing in the reference: its reads live in Python strings) ----
+ * for what sits in front of the scan or behind the partition on the same GPU: no trip over PCIe for data already in HBM.
+ * qcat_batch_from_device makes an OWNED batch by copying device memory of the context's device, device to device on the
+ * context's stream, into buffers with the library's slack and alignment -- not a view: the kernels rely on both.  The caller's
+ * data must be complete on entry, or produced on qcat_ctx_stream(ctx).  d_qualities may be NULL (no quality plane); d_offsets:
+ * n_reads + 1 uint64.  Nothing is trusted: every pointer must be device memory of this device (hipPointerGetAttributes), its
+ * allocation must hold (n_reads + 1) * 8 bytes behind d_offsets and offsets[n_reads] bytes behind d_bases / d_qualities
+ * (hipMemGetAddressRange), and a kernel checks offsets[0] == 0 and that no offset decreases, before anything is allocated or
+ * copied.  Every failed check: QCAT_ERR_ARG with a message, the context stays usable.  Synchronises. */
+int  qcat_batch_from_device(qcat_ctx* ctx, const void* d_bases, const void* d_qualities,
+                            const void* d_offsets, uint32_t n_reads, qcat_batch** out);
+/* the batch's device arrays (any of the three may be NULL = not asked for): read-only for the caller, valid until
+ * qcat_batch_destroy; *qualities = NULL without a plane.  The bases and the qualities start 64 bytes into a 256-byte aligned
+ * allocation each.  A batch that is not whole reads of its own (what the partition refuses): QCAT_ERR_ARG. */
+int  qcat_batch_devptrs(const qcat_batch* batch, const void** bases, const void** qualities, const void** offsets);
+
 /* the latest partition of this context: bin b = reads [bin_first[b], bin_first[b+1]) of `out`
  * (n_bins + 1 entries); source[i] = index in the input batch of read i of `out` (n_reads entries, may be NULL) */
 int  qcat_ctx_fetch_partition(qcat_ctx* ctx, uint64_t* bin_first, int32_t n_bins, uint32_t* source);

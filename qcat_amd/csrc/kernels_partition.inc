@@ -7,7 +7,9 @@
 //   k_part_gather    slice lengths and source positions in sorted order
 //   k_part_bins      first read of every bin
 //   k_part_chunks    first segment of every 32 KiB chunk of the output
-//   k_part_copy      the segmented copy: 16-byte aligned stores, one owner per destination vector (partition_core.h)
+//   k_part_copy      the segmented copy: 16-byte aligned stores, one owner per destination vector (partition_core.h), of one
+//                    plane (bases) or two (bases and qualities) in one pass
+//   k_offsets_check  qcat_batch_from_device: the caller's offsets start at 0 and never decrease
 // Included by qcat_hip.hip.
 #include "partition_core.h"
 
@@ -207,10 +209,16 @@ k_part_chunks(const uint64_t* __restrict__ dst_off, uint32_t n, uint32_t* __rest
 // boundaries and source positions go to the LDS; a lane finds a vector's segment there and gathers it from the two aligned
 // source vectors around its source position (qpart::gather_vector).  The grid is sized by the INPUT's bases -- the
 // output's size is known on the device only -- and a workgroup behind the output's end leaves at once.
+// P planes (1: the bases; 2: bases and qualities, one byte per base on the same offsets, both allocations aligned alike):
+// the LDS table, the segment search, the source offset, the shift and the byte masks of a destination vector are computed
+// once and applied to P loads (or load pairs) and P stores (qpart::gather_vectors).  P = 1 ignores src1 / dst1.
 // ---------------------------------------------------------------------------------------------
+template <uint32_t P>
 __global__ void __launch_bounds__(256)
 k_part_copy(const uint64_t* __restrict__ dst_off, const uint64_t* __restrict__ src_pos, uint32_t n,
-            const uint32_t* __restrict__ chunk_first, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
+            const uint32_t* __restrict__ chunk_first, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+            const uint8_t* __restrict__ src1, uint8_t* __restrict__ dst1) {
+    static_assert(P == 1 || P == 2, "one or two planes");
     __shared__ uint64_t s_off[qpart::PART_LDS_SEGS + 1];
     __shared__ uint64_t s_src[qpart::PART_LDS_SEGS];
     const uint64_t total = dst_off[n];
@@ -231,20 +239,34 @@ k_part_copy(const uint64_t* __restrict__ dst_off, const uint64_t* __restrict__ s
         }
         __syncthreads();
     }
-    const auto load16 = [&](int64_t a) {
-        const uint4 v = *reinterpret_cast<const uint4*>(src + a);
+    const auto load16 = [&](uint32_t k, int64_t a) {           // (k is a constant after unrolling)
+        const uint4 v = *reinterpret_cast<const uint4*>((k == 0 ? src : src1) + a);
         qpart::Vec16 o; o.w[0] = v.x; o.w[1] = v.y; o.w[2] = v.z; o.w[3] = v.w;
         return o;
     };
     for (uint32_t it = 0; it < qpart::PART_VECS_PER_LANE; ++it) {
         const uint64_t d0 = c0 + ((uint64_t)it * 256u + threadIdx.x) * qpart::PART_VEC;
         if (d0 >= cend) break;
-        qpart::Vec16 v;
+        qpart::Vec16 v[P];
         if (in_lds)
-            v = qpart::gather_vector([&](uint32_t j) { return s_off[j]; }, [&](uint32_t j) { return s_src[j]; }, load16, 0u, m, d0, total);
+            qpart::gather_vectors<P>([&](uint32_t j) { return s_off[j]; }, [&](uint32_t j) { return s_src[j]; }, load16, 0u, m, d0, total, v);
         else
-            v = qpart::gather_vector(goff, [&](uint32_t j) { return src_pos[j]; }, load16, jf, jl + 1u, d0, total);
-        *reinterpret_cast<uint4*>(dst + d0) = make_uint4(v.w[0], v.w[1], v.w[2], v.w[3]);
+            qpart::gather_vectors<P>(goff, [&](uint32_t j) { return src_pos[j]; }, load16, jf, jl + 1u, d0, total, v);
+        *reinterpret_cast<uint4*>(dst + d0) = make_uint4(v[0].w[0], v[0].w[1], v[0].w[2], v[0].w[3]);
+        if constexpr (P == 2) *reinterpret_cast<uint4*>(dst1 + d0) = make_uint4(v[P - 1].w[0], v[P - 1].w[1], v[P - 1].w[2], v[P - 1].w[3]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// e. the offsets of a batch made from a caller's device memory (qcat_batch_from_device): offsets[0] == 0 and no entry below
+// the one in front of it, n + 1 entries.  A grid-stride compare of neighbours; a lane that finds a fault stores 1 to *bad
+// (every such store writes the same value; the host zeroes the flag before the launch).  No workgroup waits for another.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_offsets_check(const uint64_t* __restrict__ offsets, uint32_t n, uint32_t* __restrict__ bad) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const bool wrong = i == 0 ? offsets[0] != 0 : offsets[i] < offsets[i - 1];
+        if (wrong) *bad = 1u;
     }
 }
 

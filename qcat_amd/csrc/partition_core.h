@@ -1,7 +1,8 @@
 // partition_core.h -- the lane arithmetic of the stable partition of a resident batch (kernels_partition.inc), as pure
 // functions that compile for host and device: the kept slice of a read, the search of a destination byte's read in the
 // output offsets, the ownership of a 16-byte destination vector and its assembly from aligned 16-byte source vectors.
-// tests/partition_check.cpp runs the copy kernel's chunk and lane schedule through these on the host.
+// tests/partition_check.cpp runs the copy kernel's chunk and lane schedule through these on the host, tests/partition_planes_check.cpp
+// its two-plane form.
 //
 // Vocabulary.  The output is the concatenation of n segments (the kept slices in sorted order); dst_off[0..n] are their
 // byte offsets in the output (dst_off[n] = total), src_pos[j] the byte offset of segment j's first byte in the input.
@@ -100,10 +101,15 @@ QP_HD uint32_t byte_mask(uint32_t p, uint32_t q, uint32_t i) {
 // its place in the destination vector) to less than n_bases + 32, both inside the batch's slack of 64 bytes.
 // Per overlapping segment: the two aligned vectors around the virtual source start are loaded and shifted, never single
 // bytes; a vector inside one segment -- nearly all of them -- takes one round.
-template <class Off, class Src, class Load>
-QP_HD Vec16 gather_vector(const Off& off, const Src& src, const Load& load16, uint32_t seg_lo, uint32_t seg_hi,
-                          uint64_t d0, uint64_t total) {
-    Vec16 out; out.w[0] = out.w[1] = out.w[2] = out.w[3] = 0u;
+//
+// A batch may hold P PLANES of one byte per base (bases, qualities) on the same offsets, in allocations with the same slack
+// and the same alignment: one destination vector of every plane has the same segments, source offset, shift and byte masks.
+// gather_vectors walks the segments ONCE and applies them to P loads and P output vectors; load16(k, a) is plane k's
+// aligned source vector at offset a.
+template <uint32_t P, class Off, class Src, class Load>
+QP_HD void gather_vectors(const Off& off, const Src& src, const Load& load16, uint32_t seg_lo, uint32_t seg_hi,
+                          uint64_t d0, uint64_t total, Vec16 (&out)[P]) {
+    for (uint32_t k = 0; k < P; ++k) out[k].w[0] = out[k].w[1] = out[k].w[2] = out[k].w[3] = 0u;
     const uint64_t vend = d0 + PART_VEC < total ? d0 + PART_VEC : total;
     uint64_t d = d0;
     uint32_t lo = seg_lo;
@@ -116,15 +122,26 @@ QP_HD Vec16 gather_vector(const Off& off, const Src& src, const Load& load16, ui
         const int64_t s0 = (int64_t)(src(j) + (d - seg_begin)) - (int64_t)p;
         const int64_t a = s0 & ~(int64_t)15;
         const uint32_t sh = (uint32_t)(s0 - a);
-        const Vec16 v_lo = load16(a);
-        Vec16 v = v_lo;
-        if (sh) v = shift_pair(v_lo, load16(a + 16), sh);
-        if (p == 0 && q == PART_VEC) return v;
-        for (uint32_t i = 0; i < 4; ++i) { const uint32_t m = byte_mask(p, q, i); out.w[i] = (out.w[i] & ~m) | (v.w[i] & m); }
+        Vec16 v[P];
+        for (uint32_t k = 0; k < P; ++k) v[k] = load16(k, a);
+        if (sh) for (uint32_t k = 0; k < P; ++k) v[k] = shift_pair(v[k], load16(k, a + 16), sh);
+        if (p == 0 && q == PART_VEC) { for (uint32_t k = 0; k < P; ++k) out[k] = v[k]; return; }
+        for (uint32_t i = 0; i < 4; ++i) {
+            const uint32_t m = byte_mask(p, q, i);
+            for (uint32_t k = 0; k < P; ++k) out[k].w[i] = (out[k].w[i] & ~m) | (v[k].w[i] & m);
+        }
         d = e;
         lo = j;
     }
-    return out;
+}
+
+// one plane: load16(a)
+template <class Off, class Src, class Load>
+QP_HD Vec16 gather_vector(const Off& off, const Src& src, const Load& load16, uint32_t seg_lo, uint32_t seg_hi,
+                          uint64_t d0, uint64_t total) {
+    Vec16 out[1];
+    gather_vectors<1>(off, src, [&](uint32_t, int64_t a) { return load16(a); }, seg_lo, seg_hi, d0, total, out);
+    return out[0];
 }
 
 }  // namespace qpart

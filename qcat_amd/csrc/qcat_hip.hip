@@ -456,6 +456,8 @@ struct qcat_batch {
     uint8_t* bases_alloc = nullptr;   // BATCH_SLACK + n_bases + BATCH_SLACK bytes
     uint8_t* bases = nullptr;      // bases_alloc + BATCH_SLACK: k_pack_windows reads whole aligned dwords
                                    // up to 19 bytes before / after a read's window
+    uint8_t* quals_alloc = nullptr;   // the quality plane (null: none): one byte per base on the same offsets, an allocation of
+    uint8_t* quals = nullptr;         // its own laid out like the bases'; no scan reads it, the partition moves it with the bases
     uint64_t* offsets = nullptr;   // n_reads + 1
     uint32_t* true_len = nullptr;  // window-only batches (batch_upload_windows): the reads' real lengths
     bool borrowed = false;         // the device buffers belong to a context (host-buffer calls): destroy frees the shell only
@@ -516,6 +518,7 @@ struct qcat_ctx {
         uint32_t n_reads = 0;
         int32_t n_bins = 0;                        // 0: no partition yet
     } part;
+    DevBuf<uint32_t> offs_bad;                     // qcat_batch_from_device: the flag of k_offsets_check
     // device staging of the host-buffer calls (qcat_scan_batch / _auto / _debug, qcat_detect_kit): grown on demand and
     // reused -- a 4000-read batch of the reference driver's call shape spent a third of its call in six hipMalloc / hipFree
     DevBuf<uint8_t> hb_bases;
@@ -1062,17 +1065,20 @@ extern "C" void qcat_batch_destroy(qcat_batch* b) {
     if (!b) return;
     int cur = 0; (void)hipGetDevice(&cur);
     (void)hipSetDevice(b->device);
-    if (!b->borrowed) { (void)hipFree(b->bases_alloc); (void)hipFree(b->offsets); (void)hipFree(b->true_len); }
+    if (!b->borrowed) { (void)hipFree(b->bases_alloc); (void)hipFree(b->quals_alloc); (void)hipFree(b->offsets); (void)hipFree(b->true_len); }
     (void)hipSetDevice(cur);
     delete b;
 }
 
-// the device arrays of a batch of b->n_reads reads and b->n_bases bases (fixed size, the caller's: no generation bump)
-static int batch_alloc(qcat_batch* b, const char* err) {
+// the device arrays of a batch of b->n_reads reads and b->n_bases bases (fixed size, the caller's: no generation bump);
+// with_quals: a quality plane as well, laid out like the bases
+static int batch_alloc(qcat_batch* b, const char* err, bool with_quals = false) {
     hipError_t e1 = hipMalloc((void**)&b->bases_alloc, b->n_bases + 2 * BATCH_SLACK);
     if (e1 == hipSuccess) b->bases = b->bases_alloc + BATCH_SLACK;
     hipError_t e2 = hipMalloc((void**)&b->offsets, ((size_t)b->n_reads + 1) * 8);
-    if (e1 != hipSuccess || e2 != hipSuccess) return set_err(QCAT_ERR_NOMEM, err);
+    hipError_t e3 = with_quals ? hipMalloc((void**)&b->quals_alloc, b->n_bases + 2 * BATCH_SLACK) : hipSuccess;
+    if (with_quals && e3 == hipSuccess) b->quals = b->quals_alloc + BATCH_SLACK;
+    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return set_err(QCAT_ERR_NOMEM, err);
     return 0;
 }
 
@@ -1083,10 +1089,11 @@ extern "C" int qcat_batch_info(const qcat_batch* b, uint32_t* n_reads, uint64_t*
     return 0;
 }
 
-extern "C" int qcat_batch_upload(qcat_ctx* c, const uint8_t* bases, const uint64_t* offsets,
-                                 uint32_t n_reads, qcat_batch** out) {
-    if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0))
-        return set_err(QCAT_ERR_ARG, "qcat_batch_upload: null argument");
+// qcat_batch_upload (with_quals false: `qualities` is not looked at) and qcat_batch_upload_fastq
+static int batch_upload_planes(qcat_ctx* c, const uint8_t* bases, const uint8_t* qualities, bool with_quals, const uint64_t* offsets,
+                               uint32_t n_reads, qcat_batch** out, const char* null_msg) {
+    if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0) || (with_quals && !qualities && n_reads && offsets[n_reads] > 0))
+        return set_err(QCAT_ERR_ARG, null_msg);
     if (offsets[0] != 0) return set_err(QCAT_ERR_ARG, "offsets[0] must be 0");
     for (uint32_t r = 0; r < n_reads; ++r)
         if (offsets[r + 1] < offsets[r]) return set_err(QCAT_ERR_ARG, "offsets must be non-decreasing");
@@ -1094,12 +1101,28 @@ extern "C" int qcat_batch_upload(qcat_ctx* c, const uint8_t* bases, const uint64
     qcat_batch* b = new qcat_batch();
     BatchGuard guard(b);
     b->device = c->device; b->n_reads = n_reads; b->n_bases = offsets[n_reads];
-    if (int rc = batch_alloc(b, "hipMalloc failed for batch")) return rc;
-    if (b->n_bases) HIPCHK(hipMemcpyAsync(b->bases, bases, b->n_bases, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b->offsets, offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_alloc(b, "hipMalloc failed for batch", with_quals)) return rc;
+    if (b->n_bases) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->bases, bases, b->n_bases, hipMemcpyHostToDevice, c->stream));
+    if (with_quals && b->n_bases) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->quals, qualities, b->n_bases, hipMemcpyHostToDevice, c->stream));
+    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->offsets, offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     *out = guard.release();
     return 0;
+}
+
+extern "C" int qcat_batch_upload(qcat_ctx* c, const uint8_t* bases, const uint64_t* offsets,
+                                 uint32_t n_reads, qcat_batch** out) {
+    return batch_upload_planes(c, bases, nullptr, false, offsets, n_reads, out, "qcat_batch_upload: null argument");
+}
+
+extern "C" int qcat_batch_upload_fastq(qcat_ctx* c, const uint8_t* bases, const uint8_t* qualities, const uint64_t* offsets,
+                                       uint32_t n_reads, qcat_batch** out) {
+    return batch_upload_planes(c, bases, qualities, true, offsets, n_reads, out, "qcat_batch_upload_fastq: null argument");
+}
+
+extern "C" int qcat_batch_has_qualities(const qcat_batch* b) {
+    if (!b) return set_err(QCAT_ERR_ARG, "null batch");
+    return b->quals ? 1 : 0;
 }
 
 // Host-buffer entry points scan only the first / last max_align_length bases of a read, so that is
@@ -1277,6 +1300,86 @@ extern "C" int qcat_batch_download(qcat_ctx* c, const qcat_batch* b, uint8_t* ba
     return 0;
 }
 
+extern "C" int qcat_batch_download_qualities(qcat_ctx* c, const qcat_batch* b, uint8_t* qualities) {
+    if (!c || !b) return set_err(QCAT_ERR_ARG, "qcat_batch_download_qualities: null argument");
+    if (!b->quals) return set_err(QCAT_ERR_ARG, "qcat_batch_download_qualities: the batch has no quality plane");
+    if (!qualities && b->n_bases) return set_err(QCAT_ERR_ARG, "qcat_batch_download_qualities: null argument");
+    HIPCHK(hipSetDevice(c->device));
+    if (b->n_bases) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(qualities, b->quals, b->n_bases, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// batches from and as device pointers
+// ------------------------------------------------------------------------------------------
+// `p` is device memory of `device` (not host, not managed) with at least `bytes` bytes of its allocation behind it
+static bool devmem_holds(const void* p, int device, uint64_t bytes) {
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }      // (a plain host pointer: an error, or "unregistered")
+    if (at.type != hipMemoryTypeDevice || at.isManaged || at.device != device) return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const uintptr_t lo = (uintptr_t)base, at_p = (uintptr_t)p;
+    return at_p >= lo && at_p - lo <= size && (uint64_t)(size - (at_p - lo)) >= bytes;
+}
+
+extern "C" int qcat_batch_from_device(qcat_ctx* c, const void* d_bases, const void* d_qualities, const void* d_offsets,
+                                      uint32_t n_reads, qcat_batch** out) {
+    // nothing is trusted: a wrong offset would make a later kernel read out of bounds.  The checks in this order; nothing in
+    // front of the final copies touches a byte that has not been checked.
+    if (!c || !d_bases || !d_offsets || !out) return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: null argument");
+    if ((uintptr_t)d_offsets & 7u) return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: d_offsets is not aligned to 8 bytes");
+    HIPCHK(hipSetDevice(c->device));
+    const uint64_t off_bytes = ((uint64_t)n_reads + 1) * 8;
+    // device memory of this device, every pointer (zero bytes asked for: the attributes alone)
+    if (!devmem_holds(d_offsets, c->device, 0) || !devmem_holds(d_bases, c->device, 0) || (d_qualities && !devmem_holds(d_qualities, c->device, 0)))
+        return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: a pointer is not device memory of the context's device");
+    if (!devmem_holds(d_offsets, c->device, off_bytes))
+        return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: the allocation behind d_offsets is shorter than n_reads + 1 offsets");
+    const uint64_t* offs = static_cast<const uint64_t*>(d_offsets);
+    uint64_t ends[2] = {0, 0};                                 // offsets[0], offsets[n_reads]
+    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&ends[0], offs, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&ends[1], offs + n_reads, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint64_t total = ends[1];
+    if (!devmem_holds(d_bases, c->device, total) || (d_qualities && !devmem_holds(d_qualities, c->device, total)))
+        return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: the allocation behind d_bases / d_qualities is shorter than offsets[n_reads] bytes");
+    int rc;
+    if ((rc = grow(c->offs_bad, 1))) return rc;
+    HIPCHK(hipMemsetAsync(c->offs_bad, 0, 4, c->stream));
+    hipLaunchKernelGGL(k_offsets_check, dim3(std::min<uint32_t>(n_reads / 256 + 1, 4096)), dim3(256), 0, c->stream, offs, n_reads, c->offs_bad.get());
+    uint32_t bad = 0;
+    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&bad, c->offs_bad, 4, hipMemcpyDeviceToHost, c->stream));
+    hipError_t es = hipStreamSynchronize(c->stream);
+    if (es == hipSuccess) es = hipGetLastError();
+    if (es != hipSuccess) return set_err(QCAT_ERR_DEVICE, std::string("qcat_batch_from_device: ") + hipGetErrorString(es));
+    if (bad || ends[0] != 0) return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: offsets[0] must be 0 and the offsets non-decreasing");
+    // an owned batch with the library's slack and alignment (the kernels rely on both): device-to-device on the context's stream
+    qcat_batch* b = new qcat_batch();
+    BatchGuard guard(b);
+    b->device = c->device; b->n_reads = n_reads; b->n_bases = total;
+    if ((rc = batch_alloc(b, "hipMalloc failed for batch", d_qualities != nullptr))) return rc;
+    if (total) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->bases, d_bases, total, hipMemcpyDeviceToDevice, c->stream));
+    if (total && d_qualities) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->quals, d_qualities, total, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->offsets, d_offsets, off_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *out = guard.release();
+    return 0;
+}
+
+extern "C" int qcat_batch_devptrs(const qcat_batch* b, const void** bases, const void** qualities, const void** offsets) {
+    if (!b) return set_err(QCAT_ERR_ARG, "qcat_batch_devptrs: null batch");
+    if (b->true_len || b->borrowed)
+        return set_err(QCAT_ERR_ARG, "qcat_batch_devptrs: the batch holds read windows or borrowed buffers, not whole reads of its own");
+    if (bases) *bases = b->bases;
+    if (qualities) *qualities = b->quals;
+    if (offsets) *offsets = b->offsets;
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // stable partition of a resident batch by barcode (kernels_partition.inc)
 // ------------------------------------------------------------------------------------------
@@ -1330,7 +1433,7 @@ extern "C" int qcat_batch_partition(qcat_ctx* c, const qcat_kit* ckit, const qca
     qcat_batch* ob = new qcat_batch();
     BatchGuard guard(ob);
     ob->device = c->device; ob->n_reads = n; ob->n_bases = b->n_bases;
-    if ((rc = batch_alloc(ob, "hipMalloc failed for the partitioned batch"))) return rc;
+    if ((rc = batch_alloc(ob, "hipMalloc failed for the partitioned batch", b->quals != nullptr))) return rc;
 
     auto& P = c->part;
     P.n_bins = 0; P.source = nullptr;                        // (a failure below leaves no partition behind)
@@ -1375,9 +1478,15 @@ extern "C" int qcat_batch_partition(qcat_ctx* c, const qcat_kit* ckit, const qca
     if (max_chunks) hipLaunchKernelGGL(k_part_chunks, dim3((uint32_t)((max_chunks + 255) / 256)), dim3(256), 0, c->stream,
                                        (const uint64_t*)ob->offsets, n, P.chunk_first.get(), max_chunks);
     mark(c, "part_offsets");
-    // d. the copy
-    if (max_chunks) hipLaunchKernelGGL(k_part_copy, dim3((uint32_t)max_chunks), dim3(256), 0, c->stream, (const uint64_t*)ob->offsets,
-                                       (const uint64_t*)P.src_pos.get(), n, (const uint32_t*)P.chunk_first.get(), (const uint8_t*)b->bases, ob->bases);
+    // d. the copy: the bases, and a quality plane with them through the same slices in the same launch
+    if (max_chunks && !b->quals)
+        hipLaunchKernelGGL(k_part_copy<1>, dim3((uint32_t)max_chunks), dim3(256), 0, c->stream, (const uint64_t*)ob->offsets,
+                           (const uint64_t*)P.src_pos.get(), n, (const uint32_t*)P.chunk_first.get(), (const uint8_t*)b->bases, ob->bases,
+                           (const uint8_t*)nullptr, (uint8_t*)nullptr);
+    else if (max_chunks)
+        hipLaunchKernelGGL(k_part_copy<2>, dim3((uint32_t)max_chunks), dim3(256), 0, c->stream, (const uint64_t*)ob->offsets,
+                           (const uint64_t*)P.src_pos.get(), n, (const uint32_t*)P.chunk_first.get(), (const uint8_t*)b->bases, ob->bases,
+                           (const uint8_t*)b->quals, ob->quals);
     mark(c, "part_copy");
     uint64_t total = 0;
     HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&total, ob->offsets + n, 8, hipMemcpyDeviceToHost, c->stream));

@@ -307,6 +307,22 @@ def pack_reads(read_sequences):
     return np.ascontiguousarray(bases), offsets
 
 
+def pack_qualities(qualities, offsets):
+    """list of str/bytes/None (one quality string per read) + the offsets of :func:`pack_reads` -> one uint8 array, a byte per
+    base (the quality plane of ``ResidentBatch.upload``).  ValueError when a string's length differs from its read's."""
+    lens = np.diff(np.asarray(offsets, dtype=np.uint64).astype(np.int64)).tolist()
+    if len(qualities) != len(lens):
+        raise ValueError("pack_qualities: {} quality strings for {} reads".format(len(qualities), len(lens)))
+    chunks = []
+    for i, (q, n) in enumerate(zip(qualities, lens)):
+        b = b"" if q is None else (q.encode("latin-1", "replace") if isinstance(q, str) else bytes(q))
+        if len(b) != n:
+            raise ValueError("pack_qualities: read {} has {} bases and {} quality values".format(i, n, len(b)))
+        chunks.append(b)
+    raw = b"".join(chunks)
+    return np.ascontiguousarray(np.frombuffer(raw, dtype=np.uint8)) if raw else np.zeros(1, dtype=np.uint8)
+
+
 def _ptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
 
@@ -368,6 +384,11 @@ class HipLibrary(object):
             "qcat_batch_destroy": (None, [vp]),
             "qcat_batch_info": (C.c_int, [vp, C.POINTER(u32), C.POINTER(C.c_uint64)]),
             "qcat_batch_download": (C.c_int, [vp, vp, vp, vp]),
+            "qcat_batch_upload_fastq": (C.c_int, [vp, vp, vp, vp, u32, C.POINTER(vp)]),
+            "qcat_batch_has_qualities": (C.c_int, [vp]),
+            "qcat_batch_download_qualities": (C.c_int, [vp, vp, vp]),
+            "qcat_batch_from_device": (C.c_int, [vp, vp, vp, vp, u32, C.POINTER(vp)]),
+            "qcat_batch_devptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
             "qcat_synth_read": (C.c_int64, [vp, C.POINTER(SynthParams), C.c_uint64, vp, C.c_uint64]),
             "qcat_scan_resident": (C.c_int, [vp, vp, vp]),
             "qcat_ctx_synchronize": (C.c_int, [vp]),
@@ -595,14 +616,54 @@ class ResidentBatch(object):
         self.handle = handle
 
     @classmethod
-    def upload(cls, ctx, bases, offsets):
-        """the reads of :func:`pack_reads` (uint8 bases, uint64 offsets[n + 1])"""
+    def upload(cls, ctx, bases, offsets, qualities=None):
+        """the reads of :func:`pack_reads` (uint8 bases, uint64 offsets[n + 1]); ``qualities``: the plane of
+        :func:`pack_qualities`, one byte per base (qcat_batch_upload_fastq)"""
         hip = HipLibrary.get()
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         h = C.c_void_p()
-        hip.check(hip.lib.qcat_batch_upload(ctx.handle, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, C.byref(h)))
+        if qualities is None:
+            hip.check(hip.lib.qcat_batch_upload(ctx.handle, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, C.byref(h)))
+            return cls(ctx, h)
+        qualities = np.ascontiguousarray(qualities, dtype=np.uint8)
+        if len(qualities) < int(offsets[-1]) or len(bases) < int(offsets[-1]):
+            raise ValueError("upload: {} bases and {} quality bytes for offsets that end at {}".format(len(bases), len(qualities), int(offsets[-1])))
+        hip.check(hip.lib.qcat_batch_upload_fastq(ctx.handle, bases.ctypes.data, qualities.ctypes.data, offsets.ctypes.data,
+                                                  len(offsets) - 1, C.byref(h)))
         return cls(ctx, h)
+
+    @classmethod
+    def from_device(cls, ctx, bases_ptr, offsets_ptr, n_reads, qualities_ptr=None):
+        """qcat_batch_from_device: an owned copy of reads that already live in device memory of the context's device
+        (integer addresses; ``offsets_ptr``: n_reads + 1 uint64).  The data must be complete, or produced on the context's
+        stream.  Every pointer and the offsets are checked before anything is read through them."""
+        hip = HipLibrary.get()
+        h = C.c_void_p()
+        hip.check(hip.lib.qcat_batch_from_device(ctx.handle, C.c_void_p(bases_ptr), C.c_void_p(qualities_ptr), C.c_void_p(offsets_ptr),
+                                                 int(n_reads), C.byref(h)))
+        return cls(ctx, h)
+
+    @property
+    def has_qualities(self):
+        rc = self.hip.lib.qcat_batch_has_qualities(self.handle)
+        if rc < 0:
+            self.hip.check(rc)
+        return bool(rc)
+
+    def download_qualities(self):
+        """the quality plane (uint8, one byte per base) copied back to the host; RuntimeError without a plane"""
+        nb = self.info()[1]
+        out = np.zeros(nb, dtype=np.uint8)
+        self.hip.check(self.hip.lib.qcat_batch_download_qualities(self.ctx.handle, self.handle, out.ctypes.data if nb else None))
+        return out
+
+    def devptrs(self):
+        """(bases, qualities or None, offsets): the batch's device arrays as integer addresses -- read-only, valid until
+        :meth:`destroy`"""
+        b, q, o = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.hip.check(self.hip.lib.qcat_batch_devptrs(self.handle, C.byref(b), C.byref(q), C.byref(o)))
+        return b.value, q.value, o.value
 
     @classmethod
     def synthesize(cls, ctx, kit, params):
@@ -658,6 +719,7 @@ class Partition(object):
     def __init__(self, batch, bin_first, source):
         self.batch, self.bin_first, self.source = batch, bin_first, source
         self._host = None
+        self._host_quals = None
 
     @property
     def n_bins(self):
@@ -669,6 +731,14 @@ class Partition(object):
             bases, offsets = self.batch.download()
             self._host = (bases.tobytes(), offsets.tolist())
         raw, offsets = self._host
+        return [raw[offsets[i]:offsets[i + 1]] for i in range(int(self.bin_first[b]), int(self.bin_first[b + 1]))]
+
+    def qualities(self, b):
+        """the quality strings of bin ``b`` as a list of bytes, read for read beside :meth:`reads` (the plane is downloaded
+        once, at the first call); RuntimeError for a partition of a batch without qualities"""
+        if self._host_quals is None:
+            self._host_quals = (self.batch.download_qualities().tobytes(), self.batch.download(bases=False)[1].tolist())
+        raw, offsets = self._host_quals
         return [raw[offsets[i]:offsets[i + 1]] for i in range(int(self.bin_first[b]), int(self.bin_first[b + 1]))]
 
 

@@ -441,13 +441,15 @@ class BarcodeScanner(object):
         recs, _slot = got
         return self._records_to_dicts(recs[:n], self.layouts)
 
-    def demux_batch(self, read_sequences, trim=False, min_read_length=0, qcat_config=None):
+    def demux_batch(self, read_sequences, trim=False, min_read_length=0, qcat_config=None, read_qualities=None):
         """Demultiplex a batch on the device: upload, scan, stable partition by barcode (qcat_batch_partition) -- what the
         reference driver's per-barcode writers do with a file (``qcat/cli.py:309-358`` behind ``:521-530``), for reads that
         live in device memory.  Returns ``{bin label: [(index in read_sequences, sequence), ...]}`` with the non-empty bins in
         bin order: the Barcode ids in slot order (dual mode: "id1/id2"), then "none", then "skipped" (reads the minimum-length
-        filter drops); sequences are trimmed to ``[trim5p:trim3p]`` under ``trim``.  The scanner must have ONE kit (or be a
-        simple scanner): a resident scan has one kit, and kit auto votes per batch."""
+        filter drops); sequences are trimmed to ``[trim5p:trim3p]`` under ``trim``.  With ``read_qualities`` (one quality
+        string per read, as long as the read) the entries are ``(index, sequence, quality)``: the qualities travel as a
+        second plane of the resident batch and are cut with the sequences (``qcat/cli.py:521-526``).  The scanner must have
+        ONE kit (or be a simple scanner): a resident scan has one kit, and kit auto votes per batch."""
         if qcat_config is None:
             qcat_config = config.qcatConfig()
         if not self.layouts and self._native_mode != "simple":
@@ -459,7 +461,8 @@ class BarcodeScanner(object):
         kit = self._native_kit(self.layouts, qcat_config, native.ENDS_BOTH, min_read_length=min_read_length, trim=trim)
         ctx = self._context()
         bases, offsets = native.pack_reads(read_sequences)
-        batch = native.ResidentBatch.upload(ctx, bases, offsets)
+        quals = None if read_qualities is None else native.pack_qualities(read_qualities, offsets)
+        batch = native.ResidentBatch.upload(ctx, bases, offsets, quals)
         try:
             ctx.scan_resident(kit, batch, fetch=False)
             part = ctx.partition(kit, batch)
@@ -469,7 +472,11 @@ class BarcodeScanner(object):
         source = part.source.tolist()
         for b in np.flatnonzero(np.diff(part.bin_first.astype(np.int64)) > 0).tolist():
             first = int(part.bin_first[b])
-            out[kit.descriptor.partition_label(b)] = [(source[first + i], seq.decode("latin-1")) for i, seq in enumerate(part.reads(b))]
+            if quals is None:
+                out[kit.descriptor.partition_label(b)] = [(source[first + i], seq.decode("latin-1")) for i, seq in enumerate(part.reads(b))]
+            else:
+                out[kit.descriptor.partition_label(b)] = [(source[first + i], seq.decode("latin-1"), q.decode("latin-1"))
+                                                          for i, (seq, q) in enumerate(zip(part.reads(b), part.qualities(b)))]
         part.batch.destroy()
         return out
 
