@@ -1,0 +1,74 @@
+// batch.h -- the resident batch (reads in device memory) and what belongs to it on the host (host only, like dev_buf.h): the
+// type behind qcat_batch*, its two makers' building blocks -- an owned batch allocates its planes, a view borrows a context's
+// staging -- the guard of a batch under construction, and the scratch of qcat_batch_partition / qcat_batch_from_device.
+// The functions are in batch_host.inc.  Included by qcat_hip.hip in front of middle_host.inc.
+#pragma once
+#include <memory>
+
+#include "../../include/qcat_hip.h"
+#include "dev_buf.h"
+#include "partition_core.h"
+
+constexpr size_t BATCH_SLACK = 64;                 // bytes in front of and behind a batch's bases
+static_assert(BATCH_SLACK == qpart::PART_SLACK, "the partition's copy kernel relies on the batches' slack");
+
+struct qcat_batch {
+    int device = 0;
+    uint32_t n_reads = 0;
+    uint64_t n_bases = 0;
+    uint8_t* bases = nullptr;      // BATCH_SLACK bytes into an allocation of BATCH_SLACK + n_bases + BATCH_SLACK bytes: k_pack_windows
+                                   // reads whole aligned dwords up to 19 bytes before / after a read's window
+    uint8_t* quals = nullptr;      // the quality plane (null: none): one byte per base on the same offsets, an allocation of its own
+                                   // laid out like the bases'; no scan reads it, the partition moves it with the bases
+    uint64_t* offsets = nullptr;   // n_reads + 1
+    uint32_t* true_len = nullptr;  // window-only batches (batch_upload_windows): the reads' real lengths
+
+    // the planes of a batch that owns its memory (fixed size, the caller's: no generation bump); a view -- the device buffers
+    // belong to a context (host-buffer calls) or a pipeline stage -- leaves them empty, and destroying it frees the shell only
+    struct Store {
+        qk::FixedBuf<uint8_t> bases, quals;
+        qk::FixedBuf<uint64_t> offsets;
+    } store;
+    bool owned() const { return store.bases.get() != nullptr; }
+
+    // the device arrays of an owned batch of n_reads reads and n_bases bases; with_quals: a quality plane as well
+    bool alloc(bool with_quals) {
+        const hipError_t e1 = store.bases.ensure(n_bases + 2 * BATCH_SLACK);
+        const hipError_t e2 = store.offsets.ensure((size_t)n_reads + 1);
+        const hipError_t e3 = with_quals ? store.quals.ensure(n_bases + 2 * BATCH_SLACK) : hipSuccess;
+        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return false;
+        bases = store.bases + BATCH_SLACK;
+        offsets = store.offsets;
+        if (with_quals) quals = store.quals + BATCH_SLACK;
+        return true;
+    }
+};
+
+// a view of memory that is somebody else's: `bases` points BATCH_SLACK bytes into its allocation
+static inline qcat_batch batch_view(int device, uint32_t n_reads, uint64_t n_bases, uint8_t* bases, uint64_t* offsets, uint32_t* true_len) {
+    qcat_batch v;
+    v.device = device; v.n_reads = n_reads; v.n_bases = n_bases;
+    v.bases = bases; v.offsets = offsets; v.true_len = true_len;
+    return v;
+}
+
+extern "C" void qcat_batch_destroy(qcat_batch* b);
+// owns a batch under construction, or a call's batch: destroyed on every early return, handed over with release()
+struct BatchDeleter { void operator()(qcat_batch* b) const { qcat_batch_destroy(b); } };
+using BatchPtr = std::unique_ptr<qcat_batch, BatchDeleter>;
+
+// qcat_batch_partition (kernels_partition.inc): keys, the radix sort's two (key, read index) buffers, histogram table, block
+// sums of the scans, slices, the copy's tables; `source` / `bins` belong to the latest partition
+struct PartScratch {
+    qk::DevBuf<uint32_t> key[2], idx[2], hist, sums32, chunk_first;
+    qk::DevBuf<uint64_t> start, keep, src_pos, sums64, bins;
+    qk::DevBuf<qcat_result> recs;              // records a caller handed over
+    uint32_t* source = nullptr;                // = idx[passes & 1] of the latest partition
+    uint32_t n_reads = 0;
+    int32_t n_bins = 0;                        // 0: no partition yet
+};
+// what a context keeps for the batch functions
+struct BatchScratch {
+    PartScratch part;
+    qk::DevBuf<uint32_t> offs_bad;             // qcat_batch_from_device: the flag of k_offsets_check
+};

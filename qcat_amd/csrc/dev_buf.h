@@ -1,6 +1,7 @@
 // dev_buf.h -- owners of the scan path's grow-on-demand scratch (host only): DevBuf<T> over device memory, PinBuf<T> over
 // pinned host memory.  A context, its PackedScratch and its pipeline stages hold their buffers as these types, so a buffer is
 // freed exactly once -- by its owner's destructor -- and every reallocation of device scratch goes through q_malloc.
+// FixedBuf<T> owns device memory outside that rule: the planes of a resident batch (batch.h) and the temporaries of one call.
 // Included by packed_host.inc (qcat_hip.hip, and jit_prelude.inc for the struct layouts).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +27,11 @@ struct DevMem {
 struct PinMem {                                // (no generation bump: the one pinned buffer kernels read in place bumps at its site)
     static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes); }
     static void release(void* p) { (void)hipHostFree(p); }
+};
+struct FixedMem {                              // (device memory of a fixed size that is the caller's -- the planes of a resident batch,
+                                               //  the temporaries of one call: no scan buffer moves, so no generation bump)
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void release(void* p) { (void)hipFree(p); }
 };
 
 // a pointer and its capacity in elements; move-only.  Contents are never preserved across a reallocation.
@@ -62,5 +68,6 @@ private:
 };
 template <class T> using DevBuf = ScratchBuf<T, DevMem>;
 template <class T> using PinBuf = ScratchBuf<T, PinMem>;
+template <class T> using FixedBuf = ScratchBuf<T, FixedMem>;
 
 }  // namespace qk

@@ -6,8 +6,8 @@
 //     middle_wave_leftovers  (kernels_tiny.inc, k_midw_*: the interiors the packed scan leaves, one wave per alignment)
 // and the two diagnostics that read the scratch.  The shared scan buffers (records, byte windows, PackedScratch) stay on the
 // context and are passed in.
-// Included by qcat_hip.hip after packed_host.inc and kernels_middle.inc, where qcat_batch and the error helpers of that file
-// (set_err, grow, HIPCHK) are visible: grow sites report QCAT_ERR_NOMEM, HIPCHK sites QCAT_ERR_DEVICE, the packed_* phases
+// Included by qcat_hip.hip after packed_host.inc, kernels_middle.inc and batch.h (qcat_batch), where the error helpers of that
+// file (set_err, grow, HIPCHK) are visible: grow sites report QCAT_ERR_NOMEM, HIPCHK sites QCAT_ERR_DEVICE, the packed_* phases
 // packed_last_error().
 
 // the bit-sliced interior adapter scan (kernels_abs_mid.inc, abs_mid_kernels.hip)

@@ -172,14 +172,6 @@ static inline unsigned host_threads() {
     return std::min(n, 16u);
 }
 
-// temporary device allocation released on every exit path
-struct DevTemp {
-    void* p = nullptr;
-    ~DevTemp() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
 // ------------------------------------------------------------------------------------------
 // kit
 // ------------------------------------------------------------------------------------------
@@ -448,31 +440,7 @@ static int kit_on_device(qcat_kit* k, int device, KitOnDevice** out) {
 // ------------------------------------------------------------------------------------------
 // batch (reads resident in device memory)
 // ------------------------------------------------------------------------------------------
-constexpr size_t BATCH_SLACK = 64;
-struct qcat_batch {
-    int device = 0;
-    uint32_t n_reads = 0;
-    uint64_t n_bases = 0;
-    uint8_t* bases_alloc = nullptr;   // BATCH_SLACK + n_bases + BATCH_SLACK bytes
-    uint8_t* bases = nullptr;      // bases_alloc + BATCH_SLACK: k_pack_windows reads whole aligned dwords
-                                   // up to 19 bytes before / after a read's window
-    uint8_t* quals_alloc = nullptr;   // the quality plane (null: none): one byte per base on the same offsets, an allocation of
-    uint8_t* quals = nullptr;         // its own laid out like the bases'; no scan reads it, the partition moves it with the bases
-    uint64_t* offsets = nullptr;   // n_reads + 1
-    uint32_t* true_len = nullptr;  // window-only batches (batch_upload_windows): the reads' real lengths
-    bool borrowed = false;         // the device buffers belong to a context (host-buffer calls): destroy frees the shell only
-};
-
-extern "C" void qcat_batch_destroy(qcat_batch* b);
-// owns a batch under construction: destroyed on every early return, handed over with release()
-struct BatchGuard {
-    qcat_batch* b;
-    explicit BatchGuard(qcat_batch* p) : b(p) {}
-    ~BatchGuard() { if (b) qcat_batch_destroy(b); }
-    qcat_batch* release() { qcat_batch* t = b; b = nullptr; return t; }
-    BatchGuard(const BatchGuard&) = delete;
-    BatchGuard& operator=(const BatchGuard&) = delete;
-};
+#include "batch.h"
 
 // the interior scan of --detect-middle on a resident batch: its scratch (MiddleScratch) and launch sequence
 #include "middle_host.inc"
@@ -508,17 +476,7 @@ struct qcat_ctx {
     uint32_t last_n_reads = 0;
     int last_buckets = 0;
     const qcat_kit* last_kit = nullptr;            // the kit of the scan whose records `results` holds (null: none, or a vote only)
-    // qcat_batch_partition (kernels_partition.inc): keys, the radix sort's two (key, read index) buffers, histogram table, block
-    // sums of the scans, slices, the copy's tables; `source` / `bins` belong to the latest partition
-    struct PartScratch {
-        DevBuf<uint32_t> key[2], idx[2], hist, sums32, chunk_first;
-        DevBuf<uint64_t> start, keep, src_pos, sums64, bins;
-        DevBuf<qcat_result> recs;                  // records a caller handed over
-        uint32_t* source = nullptr;                // = idx[passes & 1] of the latest partition
-        uint32_t n_reads = 0;
-        int32_t n_bins = 0;                        // 0: no partition yet
-    } part;
-    DevBuf<uint32_t> offs_bad;                     // qcat_batch_from_device: the flag of k_offsets_check
+    BatchScratch batch;                            // qcat_batch_partition and qcat_batch_from_device (batch.h)
     // device staging of the host-buffer calls (qcat_scan_batch / _auto / _debug, qcat_detect_kit): grown on demand and
     // reused -- a 4000-read batch of the reference driver's call shape spent a third of its call in six hipMalloc / hipFree
     DevBuf<uint8_t> hb_bases;
@@ -1059,557 +1017,9 @@ extern "C" int qcat_ctx_last_timing(qcat_ctx* c, const char** names, float* ms, 
 }
 
 // ------------------------------------------------------------------------------------------
-// batches: upload / download / synthetic
+// batches: upload / download / from and as device pointers / partition / synthetic (the types: batch.h)
 // ------------------------------------------------------------------------------------------
-extern "C" void qcat_batch_destroy(qcat_batch* b) {
-    if (!b) return;
-    int cur = 0; (void)hipGetDevice(&cur);
-    (void)hipSetDevice(b->device);
-    if (!b->borrowed) { (void)hipFree(b->bases_alloc); (void)hipFree(b->quals_alloc); (void)hipFree(b->offsets); (void)hipFree(b->true_len); }
-    (void)hipSetDevice(cur);
-    delete b;
-}
-
-// the device arrays of a batch of b->n_reads reads and b->n_bases bases (fixed size, the caller's: no generation bump);
-// with_quals: a quality plane as well, laid out like the bases
-static int batch_alloc(qcat_batch* b, const char* err, bool with_quals = false) {
-    hipError_t e1 = hipMalloc((void**)&b->bases_alloc, b->n_bases + 2 * BATCH_SLACK);
-    if (e1 == hipSuccess) b->bases = b->bases_alloc + BATCH_SLACK;
-    hipError_t e2 = hipMalloc((void**)&b->offsets, ((size_t)b->n_reads + 1) * 8);
-    hipError_t e3 = with_quals ? hipMalloc((void**)&b->quals_alloc, b->n_bases + 2 * BATCH_SLACK) : hipSuccess;
-    if (with_quals && e3 == hipSuccess) b->quals = b->quals_alloc + BATCH_SLACK;
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return set_err(QCAT_ERR_NOMEM, err);
-    return 0;
-}
-
-extern "C" int qcat_batch_info(const qcat_batch* b, uint32_t* n_reads, uint64_t* n_bases) {
-    if (!b) return set_err(QCAT_ERR_ARG, "null batch");
-    if (n_reads) *n_reads = b->n_reads;
-    if (n_bases) *n_bases = b->n_bases;
-    return 0;
-}
-
-// qcat_batch_upload (with_quals false: `qualities` is not looked at) and qcat_batch_upload_fastq
-static int batch_upload_planes(qcat_ctx* c, const uint8_t* bases, const uint8_t* qualities, bool with_quals, const uint64_t* offsets,
-                               uint32_t n_reads, qcat_batch** out, const char* null_msg) {
-    if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0) || (with_quals && !qualities && n_reads && offsets[n_reads] > 0))
-        return set_err(QCAT_ERR_ARG, null_msg);
-    if (offsets[0] != 0) return set_err(QCAT_ERR_ARG, "offsets[0] must be 0");
-    for (uint32_t r = 0; r < n_reads; ++r)
-        if (offsets[r + 1] < offsets[r]) return set_err(QCAT_ERR_ARG, "offsets must be non-decreasing");
-    HIPCHK(hipSetDevice(c->device));
-    qcat_batch* b = new qcat_batch();
-    BatchGuard guard(b);
-    b->device = c->device; b->n_reads = n_reads; b->n_bases = offsets[n_reads];
-    if (int rc = batch_alloc(b, "hipMalloc failed for batch", with_quals)) return rc;
-    if (b->n_bases) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->bases, bases, b->n_bases, hipMemcpyHostToDevice, c->stream));
-    if (with_quals && b->n_bases) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->quals, qualities, b->n_bases, hipMemcpyHostToDevice, c->stream));
-    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->offsets, offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *out = guard.release();
-    return 0;
-}
-
-extern "C" int qcat_batch_upload(qcat_ctx* c, const uint8_t* bases, const uint64_t* offsets,
-                                 uint32_t n_reads, qcat_batch** out) {
-    return batch_upload_planes(c, bases, nullptr, false, offsets, n_reads, out, "qcat_batch_upload: null argument");
-}
-
-extern "C" int qcat_batch_upload_fastq(qcat_ctx* c, const uint8_t* bases, const uint8_t* qualities, const uint64_t* offsets,
-                                       uint32_t n_reads, qcat_batch** out) {
-    return batch_upload_planes(c, bases, qualities, true, offsets, n_reads, out, "qcat_batch_upload_fastq: null argument");
-}
-
-extern "C" int qcat_batch_has_qualities(const qcat_batch* b) {
-    if (!b) return set_err(QCAT_ERR_ARG, "null batch");
-    return b->quals ? 1 : 0;
-}
-
-// Host-buffer entry points scan only the first / last max_align_length bases of a read, so that is
-// all they send over PCIe: every read is compacted to head + tail (reads up to 2n stay whole, which
-// keeps the two windows byte-identical), the real length travels in a separate array for the trims.
-// The compaction runs on a few host threads into pinned memory.  --detect-middle needs whole reads.
-// `ptrs` / `lens` (both or neither): the reads as one pointer and one length per read instead of the concatenated form
-// (qcat_scan_batch_ptrs: a host language that holds a string object per read passes the objects' own buffers)
-static int batch_upload_windows(qcat_ctx* c, const qcat_kit* kit, const uint8_t* bases, const uint64_t* offsets,
-                                uint32_t n_reads, qcat_batch** out, const uint8_t* const* ptrs = nullptr, const uint64_t* lens = nullptr) {
-    const DevKit& hk = kit->hk.dk;
-    // the paths that take WHOLE reads (--detect-middle: the interior scan; QCAT_HIP_FULL_UPLOAD): round 6 -- through the same pinned
-    // staging, host threads and context-owned device buffers as the windows (a read is "compacted" to all of itself).  Before,
-    // they were concatenated by one thread into pageable memory and went through qcat_batch_upload: a hipMalloc / hipFree and a
-    // pageable copy per call -- 21 ms per 173 000-read segment of the driver's file loop, whose scan takes 1 ms.  Batches
-    // of more than a gigabyte keep the plain upload (the staging is pinned memory and stays with the context).
-    const bool whole = hk.scan_middle || opt_on(QO_FULL_UPLOAD);
-    if (whole && c && (ptrs || offsets)) {
-        uint64_t tot = 0;
-        if (ptrs) for (uint32_t r = 0; r < n_reads; ++r) tot += lens[r];
-        else tot = offsets[n_reads];
-        if (tot > (1ull << 30)) {
-            std::vector<uint8_t> cat;
-            std::vector<uint64_t> cat_off;
-            if (ptrs) {
-                cat_off.resize((size_t)n_reads + 1);
-                tot = 0;
-                for (uint32_t r = 0; r < n_reads; ++r) {
-                    if (lens[r] && !ptrs[r]) return set_err(QCAT_ERR_ARG, "null read pointer");
-                    if (lens[r] > 0xFFFFFFFFull) return set_err(QCAT_ERR_UNSUPPORTED, "read longer than 4 Gb");
-                    cat_off[r] = tot; tot += lens[r];
-                }
-                cat_off[n_reads] = tot;
-                cat.resize((size_t)tot + 1);
-                for (uint32_t r = 0; r < n_reads; ++r) if (lens[r]) memcpy(cat.data() + cat_off[r], ptrs[r], (size_t)lens[r]);
-                bases = cat.data(); offsets = cat_off.data();
-            }
-            return qcat_batch_upload(c, bases, offsets, n_reads, out);
-        }
-    }
-    if (!c || !out || (!ptrs && (!offsets || (!bases && offsets[n_reads] > 0)))) return set_err(QCAT_ERR_ARG, "qcat_scan_batch: null argument");
-    if (!ptrs && offsets[0] != 0) return set_err(QCAT_ERR_ARG, "offsets[0] must be 0");
-    HIPCHK(hipSetDevice(c->device));
-    const uint64_t n = (uint64_t)hk.max_align;
-    const bool both = hk.ends == QCAT_ENDS_BOTH;
-    const uint64_t keep = whole ? ~0ull : (both ? 2 * n : n);
-    if ((size_t)n_reads + 1 > std::min(c->pin_offsets.cap(), c->pin_len.cap())) {
-        HIPCHK(c->pin_offsets.ensure((size_t)n_reads + 1));
-        HIPCHK(c->pin_len.ensure((size_t)n_reads + 1));
-        g_alloc_gen.fetch_add(1);                                      // (kernels of a handful-of-reads call read the staging in place)
-    }
-    uint64_t total = 0;
-    c->pin_offsets[0] = 0;
-    for (uint32_t r = 0; r < n_reads; ++r) {
-        if (!ptrs && offsets[r + 1] < offsets[r]) return set_err(QCAT_ERR_ARG, "offsets must be non-decreasing");
-        const uint64_t len = ptrs ? lens[r] : offsets[r + 1] - offsets[r];
-        if (ptrs && len && !ptrs[r]) return set_err(QCAT_ERR_ARG, "null read pointer");
-        if (len > 0xFFFFFFFFull) return set_err(QCAT_ERR_UNSUPPORTED, "read longer than 4 Gb");
-        c->pin_len[r] = (uint32_t)len;
-        total += len <= keep ? len : keep;
-        c->pin_offsets[r + 1] = total;
-    }
-    if (total + 1 + 2 * BATCH_SLACK > c->pin_bases.cap()) {
-        HIPCHK(c->pin_bases.ensure(total + 1 + 2 * BATCH_SLACK));                        // (slack either side like a device batch)
-        memset(c->pin_bases, 0, BATCH_SLACK);
-        g_alloc_gen.fetch_add(1);
-    }
-    uint8_t* const pin_data = c->pin_bases + BATCH_SLACK;
-    // the context's own device staging (the batch is a view of it: one host-buffer call at a time per context)
-    if (total + 2 * BATCH_SLACK > c->hb_bases.cap() && c->hb_bases.ensure((total + 2 * BATCH_SLACK) * 5 / 4) != hipSuccess)
-        return set_err(QCAT_ERR_NOMEM, "hipMalloc failed for batch");
-    if ((size_t)n_reads + 1 > std::min(c->hb_offsets.cap(), c->hb_len.cap())) {
-        const size_t want = ((size_t)n_reads + 1) * 5 / 4;
-        if (c->hb_offsets.ensure(want) != hipSuccess || c->hb_len.ensure(want) != hipSuccess)
-            return set_err(QCAT_ERR_NOMEM, "hipMalloc failed for batch");
-    }
-    uint8_t* const dev_data = c->hb_bases + BATCH_SLACK;
-    bool sent = false;                                   // the bases have gone to the device slice by slice
-    {
-        const unsigned nthreads = std::min<unsigned>(host_threads(), (unsigned)std::max<uint64_t>(1u, std::max<uint64_t>(n_reads / 16384u, total >> 23)));
-        auto work = [&](uint32_t r0, uint32_t r1) {
-            for (uint32_t r = r0; r < r1; ++r) {
-                const uint8_t* src = ptrs ? ptrs[r] : bases + offsets[r];
-                const uint64_t len = ptrs ? lens[r] : offsets[r + 1] - offsets[r];
-                uint8_t* dst = pin_data + c->pin_offsets[r];
-                if (len <= keep) { memcpy(dst, src, len); continue; }
-                memcpy(dst, src, n);
-                if (both) memcpy(dst + n, src + len - n, n);
-            }
-        };
-        std::vector<std::thread> pool;
-        // a big staging (round 6: whole reads of --detect-middle are 130 MB per segment of the file loop) in slices of ~8 MB that
-        // the workers draw from a counter: this thread sends every finished run of slices on while the others are still being
-        // copied -- the transfer hides behind the compaction instead of following it
-        const uint64_t slice_bytes = 8ull << 20;
-        if (nthreads >= 2 && total >= 4 * slice_bytes) {
-            std::vector<uint32_t> bound;                 // slice j = reads [bound[j], bound[j + 1])
-            bound.push_back(0);
-            for (uint64_t at = slice_bytes; at < total; at += slice_bytes) {
-                const uint32_t r = (uint32_t)(std::lower_bound(c->pin_offsets.get(), c->pin_offsets + n_reads, at) - c->pin_offsets);
-                if (r > bound.back() && r < n_reads) bound.push_back(r);
-            }
-            bound.push_back(n_reads);
-            const size_t n_slices = bound.size() - 1;
-            std::unique_ptr<std::atomic<uint8_t>[]> done(new std::atomic<uint8_t>[n_slices]);
-            for (size_t j = 0; j < n_slices; ++j) done[j].store(0, std::memory_order_relaxed);
-            std::atomic<size_t> next{0};
-            auto drain = [&] {
-                for (;;) {
-                    const size_t j = next.fetch_add(1);
-                    if (j >= n_slices) break;
-                    work(bound[j], bound[j + 1]);
-                    done[j].store(1, std::memory_order_release);
-                }
-            };
-            for (unsigned t = 0; t < nthreads; ++t) {
-                try { pool.emplace_back(drain); }
-                catch (const std::exception&) { break; }
-            }
-            if (pool.empty()) drain();
-            hipError_t ce = hipSuccess;
-            for (size_t j = 0; j < n_slices && ce == hipSuccess; ) {
-                while (!done[j].load(std::memory_order_acquire)) std::this_thread::yield();
-                size_t k = j + 1;
-                while (k < n_slices && done[k].load(std::memory_order_acquire)) ++k;
-                const uint64_t o0 = c->pin_offsets[bound[j]], o1 = c->pin_offsets[bound[k]];
-                if (o1 > o0) ce = hipMemcpyAsync(dev_data + o0, pin_data + o0, o1 - o0, hipMemcpyHostToDevice, c->stream);
-                j = k;
-            }
-            for (auto& th : pool) th.join();
-            if (ce != hipSuccess) { (void)hipStreamSynchronize(c->stream); return set_err(QCAT_ERR_DEVICE, std::string("upload: ") + hipGetErrorString(ce)); }
-            sent = true;
-        } else {
-            const uint32_t per = (n_reads + nthreads - 1) / nthreads;
-            uint32_t done_to = std::min<uint32_t>(n_reads, per);          // [0, per) is this thread's share
-            for (unsigned t = 1; t < nthreads; ++t) {
-                const uint32_t r0 = std::min<uint32_t>(n_reads, t * per), r1 = std::min<uint32_t>(n_reads, r0 + per);
-                if (r0 >= r1) break;
-                try { pool.emplace_back(work, r0, r1); }
-                catch (const std::exception&) { break; }                 // no more threads: the rest runs here
-                done_to = r1;
-            }
-            work(0, std::min<uint32_t>(n_reads, per));
-            if (done_to < n_reads) work(done_to, n_reads);
-            for (auto& th : pool) th.join();
-        }
-    }
-    qcat_batch* b = new qcat_batch();
-    BatchGuard guard(b);
-    b->device = c->device; b->n_reads = n_reads; b->n_bases = total; b->borrowed = true;
-    // a handful of reads (detect_barcode on one read): the kernels read the pinned staging in place -- host memory the device
-    // maps at the same address -- instead of waiting for three copies of a few hundred bytes (~4.5 us each in the call's chain)
-    if (n_reads <= 64 && !whole && !sent && !opt_on(QO_NO_ZERO_COPY)) {
-        memset(pin_data + total, 0, 1 + BATCH_SLACK);
-        b->bases_alloc = c->pin_bases; b->bases = pin_data; b->offsets = c->pin_offsets; b->true_len = c->pin_len;
-        *out = guard.release();
-        return 0;
-    }
-    b->bases_alloc = c->hb_bases; b->bases = dev_data; b->offsets = c->hb_offsets; b->true_len = c->hb_len;
-    if (total && !sent) HIPCHK(hipMemcpyAsync(b->bases, pin_data, total, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b->offsets, c->pin_offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b->true_len, c->pin_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, c->stream));
-    // (no synchronisation here: every caller hands results back to the host and drains the stream for that before it returns,
-    //  so the pinned staging is free again when the next call fills it -- one round trip less per 4000-read batch)
-    *out = guard.release();
-    return 0;
-}
-
-extern "C" int qcat_batch_download(qcat_ctx* c, const qcat_batch* b, uint8_t* bases, uint64_t* offsets) {
-    if (!c || !b) return set_err(QCAT_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    if (offsets) HIPCHK(hipMemcpyAsync(offsets, b->offsets, ((size_t)b->n_reads + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (bases && b->n_bases) HIPCHK(hipMemcpyAsync(bases, b->bases, b->n_bases, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int qcat_batch_download_qualities(qcat_ctx* c, const qcat_batch* b, uint8_t* qualities) {
-    if (!c || !b) return set_err(QCAT_ERR_ARG, "qcat_batch_download_qualities: null argument");
-    if (!b->quals) return set_err(QCAT_ERR_ARG, "qcat_batch_download_qualities: the batch has no quality plane");
-    if (!qualities && b->n_bases) return set_err(QCAT_ERR_ARG, "qcat_batch_download_qualities: null argument");
-    HIPCHK(hipSetDevice(c->device));
-    if (b->n_bases) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(qualities, b->quals, b->n_bases, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// batches from and as device pointers
-// ------------------------------------------------------------------------------------------
-// `p` is device memory of `device` (not host, not managed) with at least `bytes` bytes of its allocation behind it
-static bool devmem_holds(const void* p, int device, uint64_t bytes) {
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof at);
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }      // (a plain host pointer: an error, or "unregistered")
-    if (at.type != hipMemoryTypeDevice || at.isManaged || at.device != device) return false;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const uintptr_t lo = (uintptr_t)base, at_p = (uintptr_t)p;
-    return at_p >= lo && at_p - lo <= size && (uint64_t)(size - (at_p - lo)) >= bytes;
-}
-
-extern "C" int qcat_batch_from_device(qcat_ctx* c, const void* d_bases, const void* d_qualities, const void* d_offsets,
-                                      uint32_t n_reads, qcat_batch** out) {
-    // nothing is trusted: a wrong offset would make a later kernel read out of bounds.  The checks in this order; nothing in
-    // front of the final copies touches a byte that has not been checked.
-    if (!c || !d_bases || !d_offsets || !out) return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: null argument");
-    if ((uintptr_t)d_offsets & 7u) return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: d_offsets is not aligned to 8 bytes");
-    HIPCHK(hipSetDevice(c->device));
-    const uint64_t off_bytes = ((uint64_t)n_reads + 1) * 8;
-    // device memory of this device, every pointer (zero bytes asked for: the attributes alone)
-    if (!devmem_holds(d_offsets, c->device, 0) || !devmem_holds(d_bases, c->device, 0) || (d_qualities && !devmem_holds(d_qualities, c->device, 0)))
-        return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: a pointer is not device memory of the context's device");
-    if (!devmem_holds(d_offsets, c->device, off_bytes))
-        return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: the allocation behind d_offsets is shorter than n_reads + 1 offsets");
-    const uint64_t* offs = static_cast<const uint64_t*>(d_offsets);
-    uint64_t ends[2] = {0, 0};                                 // offsets[0], offsets[n_reads]
-    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&ends[0], offs, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&ends[1], offs + n_reads, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const uint64_t total = ends[1];
-    if (!devmem_holds(d_bases, c->device, total) || (d_qualities && !devmem_holds(d_qualities, c->device, total)))
-        return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: the allocation behind d_bases / d_qualities is shorter than offsets[n_reads] bytes");
-    int rc;
-    if ((rc = grow(c->offs_bad, 1))) return rc;
-    HIPCHK(hipMemsetAsync(c->offs_bad, 0, 4, c->stream));
-    hipLaunchKernelGGL(k_offsets_check, dim3(std::min<uint32_t>(n_reads / 256 + 1, 4096)), dim3(256), 0, c->stream, offs, n_reads, c->offs_bad.get());
-    uint32_t bad = 0;
-    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&bad, c->offs_bad, 4, hipMemcpyDeviceToHost, c->stream));
-    hipError_t es = hipStreamSynchronize(c->stream);
-    if (es == hipSuccess) es = hipGetLastError();
-    if (es != hipSuccess) return set_err(QCAT_ERR_DEVICE, std::string("qcat_batch_from_device: ") + hipGetErrorString(es));
-    if (bad || ends[0] != 0) return set_err(QCAT_ERR_ARG, "qcat_batch_from_device: offsets[0] must be 0 and the offsets non-decreasing");
-    // an owned batch with the library's slack and alignment (the kernels rely on both): device-to-device on the context's stream
-    qcat_batch* b = new qcat_batch();
-    BatchGuard guard(b);
-    b->device = c->device; b->n_reads = n_reads; b->n_bases = total;
-    if ((rc = batch_alloc(b, "hipMalloc failed for batch", d_qualities != nullptr))) return rc;
-    if (total) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->bases, d_bases, total, hipMemcpyDeviceToDevice, c->stream));
-    if (total && d_qualities) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->quals, d_qualities, total, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(b->offsets, d_offsets, off_bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *out = guard.release();
-    return 0;
-}
-
-extern "C" int qcat_batch_devptrs(const qcat_batch* b, const void** bases, const void** qualities, const void** offsets) {
-    if (!b) return set_err(QCAT_ERR_ARG, "qcat_batch_devptrs: null batch");
-    if (b->true_len || b->borrowed)
-        return set_err(QCAT_ERR_ARG, "qcat_batch_devptrs: the batch holds read windows or borrowed buffers, not whole reads of its own");
-    if (bases) *bases = b->bases;
-    if (qualities) *qualities = b->quals;
-    if (offsets) *offsets = b->offsets;
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// stable partition of a resident batch by barcode (kernels_partition.inc)
-// ------------------------------------------------------------------------------------------
-static int part_bins_of(const DevKit& hk) {
-    return (hk.mode == QCAT_MODE_DUAL ? hk.n_barcode_slots * hk.n_barcode_slots : hk.n_barcode_slots) + 2;
-}
-extern "C" int qcat_kit_partition_bins(const qcat_kit* k) { return k ? part_bins_of(k->hk.dk) : QCAT_ERR_ARG; }
-
-// records of a caller index the kit's tables on the device: every index inside them, as a scan writes them
-static bool part_records_fit(const DevKit& hk, const qcat_result* recs, uint32_t n) {
-    for (uint32_t r = 0; r < n; ++r) {
-        const qcat_result& q = recs[r];
-        if (q.adapter_idx < -1 || q.adapter_idx >= hk.nt || q.barcode_idx < -1 || q.trim5p < 0 || q.trim3p < 0) return false;
-        if (q.barcode_idx < 0) continue;
-        if (q.adapter_idx < 0 && hk.mode != QCAT_MODE_SIMPLE) continue;              // (no call: the indices are not looked at)
-        const DevTpl& t = hk.tpl[q.adapter_idx < 0 ? 0 : q.adapter_idx];
-        if (q.barcode_idx >= t.sets[0].n) return false;
-        if (hk.mode == QCAT_MODE_DUAL && (q.barcode2_idx < 0 || q.barcode2_idx >= t.sets[1].n)) return false;
-    }
-    return true;
-}
-
-extern "C" int qcat_batch_partition(qcat_ctx* c, const qcat_kit* ckit, const qcat_batch* b, const qcat_result* records,
-                                    uint32_t flags, qcat_batch** out) {
-    if (!c || !ckit || !b || !out) return set_err(QCAT_ERR_ARG, "qcat_batch_partition: null argument");
-    if (flags != 0) return set_err(QCAT_ERR_ARG, "qcat_batch_partition: flags are reserved and must be 0");
-    if (b->device != c->device) return set_err(QCAT_ERR_ARG, "qcat_batch_partition: batch lives on another device than the context");
-    if (b->true_len || b->borrowed)
-        return set_err(QCAT_ERR_ARG, "qcat_batch_partition: the batch holds read windows or borrowed buffers, not whole reads of its own");
-    qcat_kit* kit = const_cast<qcat_kit*>(ckit);
-    const DevKit& hk = kit->hk.dk;
-    const uint32_t n = b->n_reads;
-    if (!records && (c->last_kit != ckit || c->last_n_reads != n))
-        return set_err(QCAT_ERR_ARG, "qcat_batch_partition: records == NULL needs this context's latest qcat_scan_resident to be a scan of "
-                                     "these reads with this kit");
-    if (records && !part_records_fit(hk, records, n))
-        return set_err(QCAT_ERR_ARG, "qcat_batch_partition: a record indexes outside the kit's templates / barcode sets or has a negative trim");
-    if ((size_t)n + 1 >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_partition: batch too large (>= 2^31 reads)");
-    HIPCHK(hipSetDevice(c->device));
-    KitOnDevice* kd = nullptr;
-    int rc = kit_on_device(kit, c->device, &kd);
-    if (rc) return rc;
-    const KitPtrs kp{kd->kit, kd->codes, kd->ids, kd->tables};
-    const uint32_t n_bins = (uint32_t)part_bins_of(hk);
-    const uint32_t passes = qpart::key_passes(n_bins);
-    const uint32_t n_wg = (n + PART_SORT_TILE - 1) / PART_SORT_TILE;
-    const uint64_t max_chunks = qpart::chunks_of(b->n_bases);
-    if (max_chunks >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_partition: batch too large (>= 2^46 bases)");
-
-    // the output: the input's bases are an upper bound, so nothing waits for the device before the copy
-    qcat_batch* ob = new qcat_batch();
-    BatchGuard guard(ob);
-    ob->device = c->device; ob->n_reads = n; ob->n_bases = b->n_bases;
-    if ((rc = batch_alloc(ob, "hipMalloc failed for the partitioned batch", b->quals != nullptr))) return rc;
-
-    auto& P = c->part;
-    P.n_bins = 0; P.source = nullptr;                        // (a failure below leaves no partition behind)
-    for (int i = 0; i < 2; ++i) { if ((rc = grow(P.key[i], n))) return rc; if ((rc = grow(P.idx[i], n))) return rc; }
-    if ((rc = grow(P.hist, (size_t)256 * n_wg))) return rc;
-    if ((rc = grow(P.sums32, part_scan_sums((uint64_t)256 * n_wg)))) return rc;
-    if ((rc = grow(P.sums64, part_scan_sums((uint64_t)n + 1)))) return rc;
-    if ((rc = grow(P.start, n))) return rc;
-    if ((rc = grow(P.keep, n))) return rc;
-    if ((rc = grow(P.src_pos, n))) return rc;
-    if ((rc = grow(P.bins, (size_t)n_bins + 1))) return rc;
-    if ((rc = grow(P.chunk_first, (size_t)max_chunks + 1))) return rc;
-    const qcat_result* recs = c->results;
-    if (records) {
-        if ((rc = grow(P.recs, n))) return rc;
-        if (n) HIPCHK(hipMemcpyAsync(P.recs, records, (size_t)n * sizeof(qcat_result), hipMemcpyHostToDevice, c->stream));
-        recs = P.recs;
-    }
-    timing_slot(c);
-    if (c->timing) HIPCHK(hipEventRecord(c->ev[0], c->stream));
-    const uint32_t blocks_n = (n + 255) / 256;
-    // a. keys
-    if (n) hipLaunchKernelGGL(k_part_keys, dim3(std::min<uint32_t>(blocks_n, 8192)), dim3(256), 0, c->stream, kp, recs, b->offsets, n,
-                              P.key[0].get(), P.start.get(), P.keep.get());
-    mark(c, "part_keys");
-    // b. stable order: one to three passes over 8 bits of the bin
-    for (uint32_t p = 0; n && p < passes; ++p) {
-        const uint32_t* kin = P.key[p & 1]; const uint32_t* iin = p ? P.idx[p & 1].get() : nullptr;
-        hipLaunchKernelGGL(k_part_hist, dim3(n_wg), dim3(256), 0, c->stream, kin, n, 8 * p, P.hist.get(), n_wg);
-        part_scan_launch<uint32_t>(P.hist, (uint64_t)256 * n_wg, P.sums32, c->stream);
-        hipLaunchKernelGGL(k_part_scatter, dim3(n_wg), dim3(256), 0, c->stream, kin, iin, n, 8 * p, (const uint32_t*)P.hist.get(), n_wg,
-                           P.key[(p + 1) & 1].get(), P.idx[(p + 1) & 1].get());
-    }
-    const uint32_t* key_sorted = P.key[passes & 1];
-    uint32_t* source = P.idx[passes & 1];
-    mark(c, "part_order");
-    // c. output offsets (they are the output batch's offsets), first read of every bin, first segment of every chunk
-    hipLaunchKernelGGL(k_part_gather, dim3(n / 256 + 1), dim3(256), 0, c->stream, (const uint32_t*)source, (const uint64_t*)P.start.get(),
-                       (const uint64_t*)P.keep.get(), n, ob->offsets, P.src_pos.get());
-    part_scan_launch<uint64_t>(ob->offsets, (uint64_t)n + 1, P.sums64, c->stream);
-    hipLaunchKernelGGL(k_part_bins, dim3(n_bins / 256 + 1), dim3(256), 0, c->stream, key_sorted, n, n_bins, P.bins.get());
-    if (max_chunks) hipLaunchKernelGGL(k_part_chunks, dim3((uint32_t)((max_chunks + 255) / 256)), dim3(256), 0, c->stream,
-                                       (const uint64_t*)ob->offsets, n, P.chunk_first.get(), max_chunks);
-    mark(c, "part_offsets");
-    // d. the copy: the bases, and a quality plane with them through the same slices in the same launch
-    if (max_chunks && !b->quals)
-        hipLaunchKernelGGL(k_part_copy<1>, dim3((uint32_t)max_chunks), dim3(256), 0, c->stream, (const uint64_t*)ob->offsets,
-                           (const uint64_t*)P.src_pos.get(), n, (const uint32_t*)P.chunk_first.get(), (const uint8_t*)b->bases, ob->bases,
-                           (const uint8_t*)nullptr, (uint8_t*)nullptr);
-    else if (max_chunks)
-        hipLaunchKernelGGL(k_part_copy<2>, dim3((uint32_t)max_chunks), dim3(256), 0, c->stream, (const uint64_t*)ob->offsets,
-                           (const uint64_t*)P.src_pos.get(), n, (const uint32_t*)P.chunk_first.get(), (const uint8_t*)b->bases, ob->bases,
-                           (const uint8_t*)b->quals, ob->quals);
-    mark(c, "part_copy");
-    uint64_t total = 0;
-    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&total, ob->offsets + n, 8, hipMemcpyDeviceToHost, c->stream));
-    hipError_t es = hipStreamSynchronize(c->stream);
-    if (es == hipSuccess) es = hipGetLastError();
-    if (es != hipSuccess) return set_err(QCAT_ERR_DEVICE, std::string("qcat_batch_partition: ") + hipGetErrorString(es));
-    if (total > b->n_bases) return set_err(QCAT_ERR_DEVICE, "qcat_batch_partition: the slices are longer than the reads");
-    ob->n_bases = total;
-    P.source = source; P.n_reads = n; P.n_bins = (int32_t)n_bins;
-    *out = guard.release();
-    return 0;
-}
-
-extern "C" int qcat_ctx_fetch_partition(qcat_ctx* c, uint64_t* bin_first, int32_t n_bins, uint32_t* source) {
-    if (!c || !bin_first) return set_err(QCAT_ERR_ARG, "null argument");
-    if (!c->part.n_bins) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_partition: no partition on this context");
-    if (n_bins != c->part.n_bins) return set_err(QCAT_ERR_ARG, "bin count does not match the latest partition");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(bin_first, c->part.bins, ((size_t)n_bins + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (source && c->part.n_reads)
-        HIPCHK_DRAIN(c->stream, hipMemcpyAsync(source, c->part.source, (size_t)c->part.n_reads * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-extern "C" void* qcat_ctx_partition_bins_devptr(qcat_ctx* c) { return c && c->part.n_bins ? (void*)c->part.bins.get() : nullptr; }
-extern "C" void* qcat_ctx_partition_source_devptr(qcat_ctx* c) { return c && c->part.n_bins ? (void*)c->part.source : nullptr; }
-
-// --- synthetic reads ------------------------------------------------------------------------
-struct SynthSetup {
-    qsynth::Params p;
-    qsynth::Tpl t5, t3;
-    bool has5 = false, has3 = false;
-};
-
-static int synth_setup(const HostKit& hk, const qcat_synth_params* sp, const char* ascii_base, SynthSetup* s, std::string* err) {
-    if (!sp) { *err = "null synth params"; return QCAT_ERR_ARG; }
-    if (sp->lead_max < sp->lead_min) { *err = "lead_max < lead_min"; return QCAT_ERR_ARG; }
-    if (sp->error_rate < 0.f || sp->error_rate > 1.f || sp->no_adapter_fraction < 0.f || sp->no_adapter_fraction > 1.f) {
-        *err = "rates must be in [0,1]"; return QCAT_ERR_ARG;
-    }
-    s->p.seed = sp->seed; s->p.insert_len = sp->insert_len; s->p.lead_min = sp->lead_min; s->p.lead_max = sp->lead_max;
-    s->p.thr_err = (uint32_t)(sp->error_rate * 16777216.0f);
-    s->p.thr_none = (uint32_t)(sp->no_adapter_fraction * 16777216.0f);
-    auto fill = [&](int t, qsynth::Tpl* o) -> bool {
-        if (t < 0) return false;
-        const DevTpl& p = hk.dk.tpl[t];
-        o->seq = ascii_base + hk.ascii_tpl_off[t]; o->len = p.len;
-        for (int i = 0; i < 2; ++i) {
-            o->bc_start[i] = hk.bc_start[t][i]; o->bc_len[i] = p.sets[i].n > 0 ? p.bc_len[i] : 0;
-            o->n[i] = p.sets[i].n;
-            o->sets[i] = p.sets[i].n > 0 ? ascii_base + hk.ascii_set_off[t][i] : nullptr;
-        }
-        return true;
-    };
-    if (sp->tpl_5p >= hk.dk.nt || sp->tpl_3p >= hk.dk.nt) { *err = "synth template index out of range"; return QCAT_ERR_ARG; }
-    s->has5 = fill(sp->tpl_5p, &s->t5);
-    s->has3 = fill(sp->tpl_3p, &s->t3);
-    return 0;
-}
-
-extern "C" int64_t qcat_synth_read(const qcat_kit* kit, const qcat_synth_params* sp, uint64_t index,
-                                   uint8_t* buf, uint64_t cap) {
-    if (!kit) return set_err(QCAT_ERR_ARG, "null kit");
-    SynthSetup s; std::string err;
-    int rc = synth_setup(kit->hk, sp, kit->hk.ascii.data(), &s, &err);
-    if (rc) return set_err(rc, err);
-    qsynth::StoreSink sink(buf, buf ? cap : 0);
-    qsynth::generate(s.p, index, s.has5 ? &s.t5 : nullptr, s.has3 ? &s.t3 : nullptr, sink);
-    return (int64_t)sink.n;
-}
-
-__global__ void k_synth_lengths(qsynth::Params p, qsynth::Tpl t5, qsynth::Tpl t3, int has5, int has3,
-                                uint64_t first, uint32_t n, uint64_t* lens) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    qsynth::CountSink sink;
-    qsynth::generate(p, first + i, has5 ? &t5 : nullptr, has3 ? &t3 : nullptr, sink);
-    lens[i] = sink.n;
-}
-
-__global__ void k_synth_write(qsynth::Params p, qsynth::Tpl t5, qsynth::Tpl t3, int has5, int has3,
-                              uint64_t first, uint32_t n, const uint64_t* offsets, uint8_t* bases) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    qsynth::StoreSink sink(bases + offsets[i], offsets[i + 1] - offsets[i]);
-    qsynth::generate(p, first + i, has5 ? &t5 : nullptr, has3 ? &t3 : nullptr, sink);
-}
-
-extern "C" int qcat_batch_synthesize(qcat_ctx* c, const qcat_kit* ckit, const qcat_synth_params* sp, qcat_batch** out) {
-    if (!c || !ckit || !sp || !out) return set_err(QCAT_ERR_ARG, "null argument");
-    qcat_kit* kit = const_cast<qcat_kit*>(ckit);
-    HIPCHK(hipSetDevice(c->device));
-    KitOnDevice* kd = nullptr;
-    int rc = kit_on_device(kit, c->device, &kd);
-    if (rc) return rc;
-    SynthSetup s; std::string err;
-    if ((rc = synth_setup(kit->hk, sp, kd->ascii, &s, &err))) return set_err(rc, err);
-    const uint32_t n = sp->n_reads;
-    DevTemp lens_buf;
-    HIPCHK(lens_buf.alloc(((size_t)n + 1) * 8));
-    uint64_t* d_lens = lens_buf.as<uint64_t>();
-    uint32_t blocks = (n + 255) / 256;
-    // the read index space is global: `seed` identifies the data set, reads [first, first+n) are
-    // produced here (first = 0; shards pass distinct seeds or use qcat_synth_read for offsets)
-    if (n) hipLaunchKernelGGL(k_synth_lengths, dim3(blocks), dim3(256), 0, c->stream, s.p, s.t5, s.t3,
-                              (int)s.has5, (int)s.has3, (uint64_t)0, n, d_lens);
-    std::vector<uint64_t> lens((size_t)n + 1, 0), offs((size_t)n + 1, 0);
-    if (n) HIPCHK(hipMemcpyAsync(lens.data(), d_lens, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < n; ++i) offs[i + 1] = offs[i] + lens[i];
-    qcat_batch* b = new qcat_batch();
-    BatchGuard guard(b);
-    b->device = c->device; b->n_reads = n; b->n_bases = offs[n];
-    if ((rc = batch_alloc(b, "hipMalloc failed for synthetic batch"))) return rc;
-    HIPCHK(hipMemcpyAsync(b->offsets, offs.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (n) hipLaunchKernelGGL(k_synth_write, dim3(blocks), dim3(256), 0, c->stream, s.p, s.t5, s.t3,
-                              (int)s.has5, (int)s.has3, (uint64_t)0, n, b->offsets, b->bases);
-    hipError_t es = hipStreamSynchronize(c->stream);
-    if (es == hipSuccess) es = hipGetLastError();
-    if (es != hipSuccess) return set_err(QCAT_ERR_DEVICE, std::string("qcat_batch_synthesize: ") + hipGetErrorString(es));
-    *out = guard.release();
-    return 0;
-}
+#include "batch_host.inc"
 
 // ------------------------------------------------------------------------------------------
 // host-buffer entry points
@@ -1810,10 +1220,9 @@ static int scan_batch_pipelined(qcat_ctx* c, qcat_kit* kit, const ReadView& rv,
         HIPCHK(hipMemcpyAsync(st.dev_len, st.pin_len, (size_t)nr * 4, hipMemcpyHostToDevice, p->copy));
         HIPCHK(hipEventRecord(st.copied, p->copy));
         HIPCHK(hipStreamWaitEvent(c->stream, st.copied, 0));
-        qcat_batch view;                                               // the chunk as a resident batch (no ownership)
-        view.device = c->device; view.n_reads = nr; view.n_bases = total;
-        view.bases_alloc = st.dev_bases_alloc; view.bases = st.dev_bases_alloc + BATCH_SLACK;
-        view.offsets = st.dev_offsets; view.true_len = st.dev_len;
+        // the chunk as a resident batch (no ownership); its bases begin behind the front slack of the stage's allocation
+        uint8_t* const chunk_bases = st.dev_bases_alloc + BATCH_SLACK;
+        const qcat_batch view = batch_view(c->device, nr, total, chunk_bases, st.dev_offsets, st.dev_len);
         rc = scan_resident_impl(c, kit, &view, ScanPass::plain().keeping_counts(ci > 0));
         if (rc) break;
         HIPCHK(hipMemcpyAsync(st.pin_results, c->results, (size_t)nr * sizeof(qcat_result), hipMemcpyDeviceToHost, c->stream));
@@ -1858,7 +1267,7 @@ static int api_graph_run(qcat_ctx* c, qcat_ctx::ApiGraph& G, qcat_kit* kit, KitO
     const uint32_t n_reads = b->n_reads;
     auto drained = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
     static const QcatOpt no_capture[] = {QO_NO_GRAPH, QO_DEBUG_VOTE, QO_BS_TRACE, QO_DEBUG_BINS, QO_DEBUG_REDO};
-    bool graph_ok = !c->timing && G.failures < 2 && b->borrowed && !kit->hk.dk.scan_middle && !opt_on(QO_FULL_UPLOAD);      // (whole reads -- --detect-middle -- never replay)
+    bool graph_ok = !c->timing && G.failures < 2 && !b->owned() && !kit->hk.dk.scan_middle && !opt_on(QO_FULL_UPLOAD);      // (whole reads -- --detect-middle -- never replay)
     for (QcatOpt o : no_capture) if (opt_on(o)) graph_ok = false;
     const uint64_t gen_before = g_alloc_gen.load();
     bool done = false;
@@ -1914,7 +1323,7 @@ static int scan_debug_impl(qcat_ctx* c, const qcat_kit* ckit,
     if (rc) return rc;
     const bool debug = traces != nullptr || bc_rows != nullptr;
     // (whole reads -- --detect-middle -- never replay a graph: the interior scan sizes buffers from the batch)
-    if (!debug && b->borrowed && n_reads && n_reads <= 65536 && !kit->hk.dk.scan_middle && !opt_on(QO_FULL_UPLOAD)) {
+    if (!debug && !b->owned() && n_reads && n_reads <= 65536 && !kit->hk.dk.scan_middle && !opt_on(QO_FULL_UPLOAD)) {
         // the reference's library entry -- detect_barcode / detect_barcode_batch with a named kit, down to ONE read per call
         // (qcat/test/test_barcode.py:84, cli.py:504-509) -- is a dozen launches of a few microseconds each: calls of one shape
         // replay them as a graph, like the kit-auto calls (api_graph_run)
@@ -2022,7 +1431,7 @@ static int scan_batch_auto_impl(qcat_ctx* c, const qcat_kit* ckit, const uint8_t
     qcat_batch* b = nullptr;
     int rc = batch_upload_windows(c, kit, bases, offsets, n_reads, &b, ptrs, lens);
     if (rc) return rc;
-    BatchGuard guard(b);
+    BatchPtr guard(b);
     // (a failed step drains the stream before it returns: the upload may still be reading the pinned staging)
     auto drained = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
     KitOnDevice* kd = nullptr;
@@ -2228,24 +1637,27 @@ extern "C" int qcat_sg_align(qcat_ctx* c, const uint8_t* queries, const uint64_t
     c->last_tiny_ends = 0;
     const uint32_t blocks = (n + GEN_THREADS - 1) / GEN_THREADS;
     const size_t threads = (size_t)blocks * GEN_THREADS;
-    DevTemp dq, dqo, dt, dto, dscr, dout;
-    HIPCHK(dq.alloc(qb + 1)); HIPCHK(dqo.alloc(((size_t)n + 1) * 8)); HIPCHK(dt.alloc(tb + 1)); HIPCHK(dto.alloc(((size_t)n + 1) * 8));
-    if (!waves) HIPCHK(dscr.alloc((with_stats ? 6 : 2) * (size_t)(MAX_TLEN + 1) * threads * 4));
-    HIPCHK(dout.alloc((size_t)n * sizeof(qcat_alignment)));
-    if (qb) HIPCHK(hipMemcpyAsync(dq.p, queries, qb, hipMemcpyHostToDevice, c->stream));
-    if (tb) HIPCHK(hipMemcpyAsync(dt.p, targets, tb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dqo.p, q_offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dto.p, t_offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    FixedBuf<uint8_t> dq, dt;                          // (temporaries of this call: released on every exit path)
+    FixedBuf<uint64_t> dqo, dto;
+    FixedBuf<int32_t> dscr;
+    FixedBuf<qcat_alignment> dout;
+    HIPCHK(dq.ensure(qb + 1)); HIPCHK(dqo.ensure((size_t)n + 1)); HIPCHK(dt.ensure(tb + 1)); HIPCHK(dto.ensure((size_t)n + 1));
+    if (!waves) HIPCHK(dscr.ensure((with_stats ? 6 : 2) * (size_t)(MAX_TLEN + 1) * threads));
+    HIPCHK(dout.ensure(n));
+    if (qb) HIPCHK(hipMemcpyAsync(dq, queries, qb, hipMemcpyHostToDevice, c->stream));
+    if (tb) HIPCHK(hipMemcpyAsync(dt, targets, tb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dqo, q_offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dto, t_offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     SgMatrix m;
     memcpy(m.m, matrix, 49);
     if (waves)
-        hipLaunchKernelGGL(k_sg_wave, dim3(n), dim3(64), 0, c->stream, dq.as<uint8_t>(), dqo.as<uint64_t>(), dt.as<uint8_t>(),
-                           dto.as<uint64_t>(), n, (int)gap_open, (int)gap_extend, m, (int)(r1_flag != 0), dout.as<qcat_alignment>());
+        hipLaunchKernelGGL(k_sg_wave, dim3(n), dim3(64), 0, c->stream, dq.get(), dqo.get(), dt.get(),
+                           dto.get(), n, (int)gap_open, (int)gap_extend, m, (int)(r1_flag != 0), dout.get());
     else
-    hipLaunchKernelGGL(k_sg_align, dim3(blocks), dim3(GEN_THREADS), 0, c->stream, dq.as<uint8_t>(), dqo.as<uint64_t>(), dt.as<uint8_t>(),
-                       dto.as<uint64_t>(), n, (int)gap_open, (int)gap_extend, m, (int)(with_stats | r1_flag), dscr.as<int32_t>(), dout.as<qcat_alignment>());
+    hipLaunchKernelGGL(k_sg_align, dim3(blocks), dim3(GEN_THREADS), 0, c->stream, dq.get(), dqo.get(), dt.get(),
+                       dto.get(), n, (int)gap_open, (int)gap_extend, m, (int)(with_stats | r1_flag), dscr.get(), dout.get());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(qcat_alignment), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * sizeof(qcat_alignment), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->last_tiny_ends = waves ? n : 0;
     return 0;

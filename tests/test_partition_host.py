@@ -58,8 +58,9 @@ def test_the_check_and_the_kernel_share_their_constants():
     assert '#include "partition_core.h"' in text
     for name in ("qpart::gather_vector", "qpart::find_segment", "qpart::PART_CHUNK", "qpart::PART_LDS_SEGS", "qpart::slice_of"):
         assert name in text, name
-    with open(os.path.join(ROOT, "qcat_amd", "csrc", "qcat_hip.hip")) as fh:
-        hip = fh.read()
-    assert "constexpr size_t BATCH_SLACK = 64;" in hip                       # = qpart::PART_SLACK
+    with open(os.path.join(ROOT, "qcat_amd", "csrc", "batch.h")) as fh:
+        batch = fh.read()
+    assert "constexpr size_t BATCH_SLACK = 64;" in batch                     # = qpart::PART_SLACK, and the compiler holds them together
+    assert '#include "partition_core.h"' in batch and "static_assert(BATCH_SLACK == qpart::PART_SLACK" in batch
     with open(os.path.join(ROOT, "qcat_amd", "csrc", "partition_core.h")) as fh:
         assert "constexpr uint32_t PART_SLACK = 64;" in fh.read()

@@ -61,9 +61,10 @@ def test_the_kernel_takes_both_plane_counts_from_the_shared_gather():
     with open(os.path.join(ROOT, "qcat_amd", "csrc", "kernels_partition.inc")) as fh:
         text = fh.read()
     assert "qpart::gather_vectors<P>" in text and "k_offsets_check" in text
-    with open(os.path.join(ROOT, "qcat_amd", "csrc", "qcat_hip.hip")) as fh:
-        hip = fh.read()
-    assert "k_part_copy<1>" in hip and "k_part_copy<2>" in hip
+    with open(os.path.join(ROOT, "qcat_amd", "csrc", "batch_host.inc")) as fh:
+        host = fh.read()
+    # (the two launches share their argument list: one launcher over the plane count, called with 1 and with 2)
+    assert "hipLaunchKernelGGL(k_part_copy<PLANES>" in host and "part_copy_launch<1>(" in host and "part_copy_launch<2>(" in host
 
 
 def test_pack_qualities_follows_the_reads_offsets():

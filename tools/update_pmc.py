@@ -15,7 +15,7 @@ from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# kernel-name fragments -> the timing mark their launches are enclosed by (packed_host.inc / qcat_hip.hip)
+# kernel-name fragments -> the timing mark their launches are enclosed by (packed_host.inc / qcat_hip.hip; the part_* marks of the partition: batch_host.inc)
 MARKS = [
     ("k_pack_windows", "k_pack_windows"), ("k_expand_special", "k_pack_windows"), ("k_fill_multi", "k_pack_windows"),
     ("k_mid_windows", "k_middle_packed"), ("k_adapter_middle", "k_middle_packed"), ("k_middle", "k_middle_packed"), ("k_mid_", "k_middle_packed"),
