@@ -393,12 +393,45 @@ int  qcat_ctx_fetch_counts(qcat_ctx* ctx, int64_t* counts, int32_t n_buckets);
 void* qcat_ctx_counts_devptr(qcat_ctx* ctx);
 void* qcat_ctx_results_devptr(qcat_ctx* ctx);
 
+/* ---- the reference driver's per-batch semantics on a resident batch: kit vote and --filter-barcodes in HBM ----
+ * replaces, for reads that stay in HBM: the driver's loop over batches of 4000 reads (qcat/cli.py:500) with kit auto -- a kit
+ * voted per batch, detect_kit + detect_barcode_batch, qcat/scanner_base.py:662-678, :714-733 -- and with --filter-barcodes
+ * (get_valid(counts, 0.05) + filter_barcodes per batch, qcat/scanner_base.py:690-712, :730-731).
+ * qcat_scan_resident with reads [q * batch_reads, (q + 1) * batch_reads) as batch q (batch_reads == 0 or larger than the
+ * resident batch: the whole batch is one batch).  flags == 0: exactly qcat_scan_resident, the same launches.
+ * QCAT_RESIDENT_KIT_AUTO: `kit` holds the templates of every kit (kit_slot per template); every batch votes for a kit on the
+ * device and its reads are scanned with the voted kit's templates, as qcat_scan_batch_auto does for host buffers; records index
+ *   the full kit's template list.  Needs QCAT_ENDS_BOTH and no simple mode (QCAT_ERR_ARG) and a kit whose adapter pass can be
+ *   resumed per kit (QCAT_ERR_UNSUPPORTED otherwise, as qcat_scan_batch_auto).  The adapter passes take the batch in chunks of
+ *   whole vote batches (QCAT_HIP_RESIDENT_AUTO_CHUNK reads, default 2^20); a kit with scan_middle_adapter must fit one chunk
+ *   (QCAT_ERR_UNSUPPORTED with a message otherwise, before anything is scanned).
+ * QCAT_RESIDENT_FILTER_BARCODES: per batch, every barcode key is counted (`none` included), floor = int(max * 0.05), and a called
+ *   record whose key is not counted more often than the floor becomes the empty record (trims 0, exit_status 1).  Runs on the
+ *   final records -- behind the interior scan of scan_middle_adapter -- and in front of the counts: the count vector, `skipped`
+ *   included, is that of the filtered records.  Integer arithmetic only: the records are the same bytes run after run.
+ * Afterwards qcat_ctx_fetch_results / _counts and qcat_batch_partition(records = NULL) work as after qcat_scan_resident; the bins
+ * of a partition are the full kit's id slots, so one barcode id voted under two kits is one bin.  A failed call leaves no scan
+ * behind and the context usable.  Enqueues on the context's stream; every data-dependent decision is made on the device. */
+enum { QCAT_RESIDENT_KIT_AUTO = 1, QCAT_RESIDENT_FILTER_BARCODES = 2 };
+int  qcat_scan_resident_batches(qcat_ctx* ctx, const qcat_kit* kit, const qcat_batch* batch,
+                                uint32_t batch_reads, uint32_t flags);
+/* voted kit slot per batch of the context's latest qcat_scan_resident_batches with QCAT_RESIDENT_KIT_AUTO (synchronises);
+ * n_batches = ceil(n_reads / batch_reads), 1 for a single batch, 0 for an empty resident batch; a latest scan without
+ * QCAT_RESIDENT_KIT_AUTO or another n_batches: QCAT_ERR_ARG */
+int  qcat_ctx_fetch_kit_slots(qcat_ctx* ctx, int32_t* slots, uint32_t n_batches);
+/* the filter of QCAT_RESIDENT_FILTER_BARCODES alone, in place on n_reads records a caller holds on the host (indices inside the
+ * kit's tables, trims >= 0: QCAT_ERR_ARG otherwise): the same kernels, for callers with records of their own.  Synchronises;
+ * leaves the context's latest scan as it is. */
+int  qcat_filter_barcodes(qcat_ctx* ctx, const qcat_kit* kit, qcat_result* records, uint32_t n_reads,
+                          uint32_t batch_reads);
+
 /* ---- demultiplexing on the device: stable partition of a resident batch by barcode ----
  * replaces, for reads that stay in HBM: the per-barcode writers of the reference driver (qcat/cli.py:309-358 -- one output per
  * barcode, reads in file order) behind its trimming and minimum-length filter (qcat/cli.py:521-530: sequence[trim5p:trim3p],
  * reads under min_read_length are dropped).  The file path has this in csrc/fastq_host.inc; a pipeline with a basecaller in
  * front and an aligner behind gets the reads of every barcode as one contiguous run of a new resident batch.
- * A resident scan has ONE kit: a per-batch kit vote (qcat_scan_batch_auto) has no resident form, so neither has this. */
+ * The records are those of qcat_scan_resident (one kit) or of qcat_scan_resident_batches (a kit voted per batch, the barcode
+ * filter): under a vote the bins are the id slots of the full kit, one bin per barcode id whichever kit a batch voted for. */
 /* bins of a partition: [barcode buckets of the count vector .., none, skipped]
  * = (mode == DUAL ? n_slots*n_slots : n_slots) + 2 */
 int  qcat_kit_partition_bins(const qcat_kit* kit);

@@ -67,8 +67,15 @@ struct PartScratch {
     uint32_t n_reads = 0;
     int32_t n_bins = 0;                        // 0: no partition yet
 };
+// --filter-barcodes on the device (kernels_filter.inc, filter_host.inc): the key counters of a round of batches, a floor per
+// batch of the round, and the records of a caller that holds them on the host (qcat_filter_barcodes)
+struct FilterScratch {
+    qk::DevBuf<uint32_t> table, floor;
+    qk::DevBuf<qcat_result> recs;
+};
 // what a context keeps for the batch functions
 struct BatchScratch {
     PartScratch part;
+    FilterScratch filter;
     qk::DevBuf<uint32_t> offs_bad;             // qcat_batch_from_device: the flag of k_offsets_check
 };

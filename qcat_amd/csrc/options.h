@@ -58,6 +58,8 @@
     X(WAVE_MAX, "most alignments of a call (pairs of qcat_sg_align without statistics; sequences of qcat_scan_sequences with affine gap costs, sequences x barcodes with a simple list) that take the one-wave kernels (default: the limits in kernels_tiny.inc)") \
     X(AUTO_CHUNK, "batches per call of the kit-auto file loop") \
     X(AUTO_WORKERS, "contexts of the kit-auto file loop") \
+    X(RESIDENT_AUTO_CHUNK, "reads per adapter pass of a resident kit-auto scan, cut at whole vote batches (default 1048576, the file loop's)") \
+    X(FILTER_TABLE_BYTES, "bytes of the key counters of --filter-barcodes on the device: the batches are filtered in rounds that fit (default 67108864; at least one batch per round)") \
     X(NO_GRAPH, "1: host-buffer calls never replay a captured graph") \
     X(DEBUG_VOTE, "1: print the kit vote") \
     X(DEBUG_BINS, "1: print the jobs per length class") \

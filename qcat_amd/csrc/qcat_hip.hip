@@ -38,6 +38,7 @@
 #include "kernels_static.inc"
 #include "kernels_middle.inc"
 #include "kernels_partition.inc"
+#include "kernels_filter.inc"
 #include "static_registry.inc"
 #include "host_pipeline.inc"
 
@@ -476,7 +477,12 @@ struct qcat_ctx {
     uint32_t last_n_reads = 0;
     int last_buckets = 0;
     const qcat_kit* last_kit = nullptr;            // the kit of the scan whose records `results` holds (null: none, or a vote only)
-    BatchScratch batch;                            // qcat_batch_partition and qcat_batch_from_device (batch.h)
+    BatchScratch batch;                            // qcat_batch_partition, qcat_batch_from_device and the barcode filter (batch.h)
+    // qcat_scan_resident_batches: the first read of the chunk a scan writes its records for (0 outside that call), the voted
+    // kit slot of every batch of the latest kit-auto scan and their number (-1: the latest scan voted for nothing)
+    uint32_t res_first = 0;
+    DevBuf<int32_t> kit_slots;
+    int64_t auto_batches = -1;
     // device staging of the host-buffer calls (qcat_scan_batch / _auto / _debug, qcat_detect_kit): grown on demand and
     // reused -- a 4000-read batch of the reference driver's call shape spent a third of its call in six hipMalloc / hipFree
     DevBuf<uint8_t> hb_bases;
@@ -650,11 +656,13 @@ struct ScanPass {
     int resume_kit_mask = -1;           // >= 0: the adapter alignments of the vote pass are still on the device; their merge for these kit
                                         // slots (RESUME_KIT_ON_DEVICE: the slot k_pick_kit chose), the barcode phase and the finalisation
     bool keep_counts = false;           // the count vector goes on from the scan before
+    bool defer_counts = false;          // the records are not final yet (--filter-barcodes on the device): nothing is counted, the caller runs k_count
     static ScanPass plain() { return ScanPass{}; }
     static ScanPass debug(uint32_t row_stride) { ScanPass p; p.debug_scan = true; p.row_stride = row_stride; return p; }
     static ScanPass vote() { ScanPass p; p.adapter_only = true; return p; }
     static ScanPass resume(int kit_mask) { ScanPass p; p.resume_kit_mask = kit_mask; return p; }
     ScanPass keeping_counts(bool keep = true) const { ScanPass p = *this; p.keep_counts = keep; return p; }
+    ScanPass deferring_counts(bool defer = true) const { ScanPass p = *this; p.defer_counts = defer; return p; }
     bool resumed() const { return resume_kit_mask >= 0; }
 };
 
@@ -805,30 +813,33 @@ static int scan_read_ends(qcat_ctx* c, const qcat_kit* kit, KitPtrs kp, size_t n
 
 // step 5, finalise (every pass but the vote): the records of the reads and their counts; --detect-middle kits scan the
 // interiors of the called reads in between (middle_host.inc, k_scan_middle for what that leaves) and count afterwards
-static int scan_finalize(qcat_ctx* c, const DevKit& hk, KitPtrs kp, const qcat_batch* b, const ScanPath& path) {
+// (`counting` false: the caller counts -- the records still change behind this step, qcat_scan_resident_batches' filter; the
+// records go to c->results from read c->res_first on: a chunk of a resident batch)
+static int scan_finalize(qcat_ctx* c, const DevKit& hk, KitPtrs kp, const qcat_batch* b, const ScanPath& path, bool counting = true) {
     const uint32_t n = b->n_reads;
+    qcat_result* const results = c->results + c->res_first;
     // every block zeroes and flushes an LDS histogram of n_buckets entries with global atomics on the same few counters:
     // fewer, fatter blocks -- 1024 (measured, tools/r04_fin.sh: config 2 0.059 -> 0.028 ms against 4096 blocks, config 3
     // 0.235 -> 0.207 ms), 512 when the bucket vector is long (dual kits: 0.052 against 0.072 ms)
     const QOptVal fb_env = qopt_get(QO_FIN_BLOCKS);                          // (A/B runs)
     uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, fb_env ? (uint64_t)std::max(1, atoi(fb_env)) : (hk.n_buckets > 2048 ? 512 : 1024));
     const bool middle = hk.scan_middle != 0;
-    hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(256), fin_lds_bytes(hk.n_buckets, !middle), c->stream,
-                       kp, c->recs, b->offsets, b->true_len, n, c->results, middle ? nullptr : c->counts,
+    hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(256), fin_lds_bytes(hk.n_buckets, !middle && counting), c->stream,
+                       kp, c->recs, b->offsets, b->true_len, n, results, (middle || !counting) ? nullptr : c->counts.get(),
                        path.slim ? c->packed.bcres : nullptr, path.slim ? c->packed.fin : nullptr);
     mark(c, "k_finalize");
     if (!middle) return 0;
     int rc;
     const uint8_t* only = nullptr;
     if (path.middle_packed) {                              // (also after the tiny kernels: the interiors are no handful of cells)
-        if ((rc = middle_packed(c->stream, &c->middle, &c->packed, kp, hk, b, n, c->results, c->win))) return rc;
+        if ((rc = middle_packed(c->stream, &c->middle, &c->packed, kp, hk, b, n, results, c->win))) return rc;
         only = c->middle.mid_generic;                      // interiors beyond the packed path's length classes
         mark(c, "k_middle_packed");
     }
-    if ((rc = middle_wave_leftovers(c->stream, &c->middle, kp, hk, b, n, c->results, path.tiny_maxb, only && !c->force_generic))) return rc;
+    if ((rc = middle_wave_leftovers(c->stream, &c->middle, kp, hk, b, n, results, path.tiny_maxb, only && !c->force_generic))) return rc;
     hipLaunchKernelGGL(k_scan_middle, dim3((n + GEN_THREADS - 1) / GEN_THREADS), dim3(GEN_THREADS), 0, c->stream,
-                       kp, b->bases, b->offsets, n, c->results, only);
-    hipLaunchKernelGGL(k_count, dim3(blocks), dim3(256), 0, c->stream, kp, c->results, b->offsets, b->true_len, n, c->counts);
+                       kp, b->bases, b->offsets, n, results, only);
+    if (counting) hipLaunchKernelGGL(k_count, dim3(blocks), dim3(256), 0, c->stream, kp, results, b->offsets, b->true_len, n, c->counts);
     mark(c, "k_scan_middle");
     return 0;
 }
@@ -852,6 +863,7 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, c
     c->last_n_reads = n;
     c->last_buckets = hk.n_buckets;
     c->last_kit = pass.adapter_only ? nullptr : kit;
+    c->auto_batches = -1;                          // (the voted slots of an earlier qcat_scan_resident_batches belong to other records)
     timing_slot(c);
     const ScanPath path = scan_choose_path(c->force_generic != 0, hk, n_ends, pass);
     c->last_tiny_ends = path.tiny ? (uint32_t)n_ends : 0;
@@ -885,7 +897,7 @@ static int scan_resident_impl(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, c
 
     // 4. the read ends, 5. finalise
     if ((rc = scan_read_ends(c, kit, kp, n_ends, pass, path))) return rc;
-    if (!pass.adapter_only && (rc = scan_finalize(c, hk, kp, b, path))) return rc;
+    if (!pass.adapter_only && (rc = scan_finalize(c, hk, kp, b, path, !pass.defer_counts))) return rc;
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1020,6 +1032,8 @@ extern "C" int qcat_ctx_last_timing(qcat_ctx* c, const char** names, float* ms, 
 // batches: upload / download / from and as device pointers / partition / synthetic (the types: batch.h)
 // ------------------------------------------------------------------------------------------
 #include "batch_host.inc"
+// --filter-barcodes on the device: filter_run for the records of a scan, qcat_filter_barcodes for records of a caller
+#include "filter_host.inc"
 
 // ------------------------------------------------------------------------------------------
 // host-buffer entry points
@@ -1525,6 +1539,128 @@ extern "C" int qcat_scan_batches_auto_ptrs(qcat_ctx* c, const qcat_kit* ckit, co
         return scan_batch_auto_impl(c, ckit, nullptr, nullptr, reads, lengths, n_reads, out, counts, chosen_kit_slots, nullptr, nullptr);
     if ((uint64_t)(n_reads + batch_reads - 1) / batch_reads > 65535u) return set_err(QCAT_ERR_ARG, "qcat_scan_batches_auto_ptrs: more than 65535 batches in one call");
     return scan_batch_auto_impl(c, ckit, nullptr, nullptr, reads, lengths, n_reads, out, counts, chosen_kit_slots, nullptr, nullptr, batch_reads);
+}
+
+// ------------------------------------------------------------------------------------------
+// the driver's per-batch semantics on a resident batch: kit vote and --filter-barcodes without leaving the device
+// ------------------------------------------------------------------------------------------
+// what one such scan is: the batches of the vote and of the filter, and the chunks the adapter passes of a vote take them in
+struct ResidentBatchesJob {
+    uint32_t n, per, n_batches;         // per: reads of a batch (the whole resident batch when the caller gave 0 or more than it holds)
+    uint32_t chunk_batches;             // batches per adapter pass of a kit vote
+    bool kit_auto, filter;
+};
+
+static int resident_batches_check(const qcat_ctx* c, const qcat_kit* kit, const qcat_batch* b, uint32_t flags) {
+    if (!c || !kit || !b) return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: null argument");
+    if (flags & ~(uint32_t)(QCAT_RESIDENT_KIT_AUTO | QCAT_RESIDENT_FILTER_BARCODES))
+        return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: unknown flag");
+    if (b->device != c->device) return set_err(QCAT_ERR_ARG, "batch lives on another device than the context");
+    const DevKit& hk = kit->hk.dk;
+    if ((flags & QCAT_RESIDENT_KIT_AUTO) && hk.mode == QCAT_MODE_SIMPLE)
+        return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: simple mode has no kits to vote for (QCAT_RESIDENT_KIT_AUTO)");
+    if ((flags & QCAT_RESIDENT_KIT_AUTO) && hk.ends != QCAT_ENDS_BOTH)
+        return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: QCAT_RESIDENT_KIT_AUTO needs a kit created with QCAT_ENDS_BOTH");
+    return 0;
+}
+
+// the batches and the chunks; a scan this call could not finish is refused here, before anything is enqueued
+static int resident_batches_plan(const DevKit& hk, const qcat_batch* b, uint32_t batch_reads, uint32_t flags, ResidentBatchesJob& j) {
+    j.n = b->n_reads;
+    j.kit_auto = (flags & QCAT_RESIDENT_KIT_AUTO) != 0; j.filter = (flags & QCAT_RESIDENT_FILTER_BARCODES) != 0;
+    j.per = (batch_reads == 0 || batch_reads >= j.n) ? j.n : batch_reads;
+    j.n_batches = (j.n + j.per - 1) / j.per;
+    // one adapter pass over every template of every kit holds its alignments for the resumed pass: the file loop takes a
+    // million reads per call at most (fastq_host.inc), and so does this -- whole vote batches, 65535 of them at most (the
+    // grid of k_vote); a single batch larger than that is one pass, as it is for qcat_scan_resident
+    const uint64_t chunk_reads = (uint64_t)std::max<int64_t>(1, opt_val(QO_RESIDENT_AUTO_CHUNK, (int64_t)1 << 20));
+    j.chunk_batches = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(chunk_reads / j.per, 1), 65535);
+    if (!j.kit_auto || j.n_batches <= j.chunk_batches) j.chunk_batches = j.n_batches;
+    // the interior scan reads its batch from the first base on (absm_c2, the search of a base's read): it takes no view that
+    // starts inside a batch
+    if (j.kit_auto && hk.scan_middle && j.n_batches > j.chunk_batches)
+        return set_err(QCAT_ERR_UNSUPPORTED, "qcat_scan_resident_batches: a kit vote with scan_middle_adapter takes one adapter pass "
+                                             "(QCAT_HIP_RESIDENT_AUTO_CHUNK reads, 65535 batches) at most; scan the batch in parts");
+    return 0;
+}
+
+// one chunk of a kit vote: the vote pass over every template, the votes counted and decided per batch on the device, the
+// resumed pass with every read's kit slot from its batch -- scan_batch_auto_impl with a view of the resident batch where that
+// function's upload stands, the slots kept in c->kit_slots, the records from read r0 on in c->results
+static int resident_vote_chunk(qcat_ctx* c, qcat_kit* kit, KitOnDevice* kd, const qcat_batch* b, const ResidentBatchesJob& j, uint32_t q0, uint32_t qn) {
+    const uint32_t r0 = q0 * j.per, rn = (uint32_t)std::min<uint64_t>(j.n - r0, (uint64_t)qn * j.per);
+    const qcat_batch view = batch_view(b->device, rn, b->n_bases, b->bases, b->offsets + r0, nullptr);
+    const uint32_t span_reads = j.n_batches > 1 ? j.per : 0u;           // (0: one batch, one slot -- the form of qcat_scan_batch_auto)
+    int rc;
+    c->res_first = r0;
+    if ((rc = scan_resident_impl(c, kit, &view, ScanPass::vote().keeping_counts(q0 > 0)))) return rc;
+    if ((rc = vote_buffer(c, qn))) return rc;
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(c->vote_buf.get());
+    unsigned long long* d_first = d + (size_t)qn * MAX_T;
+    int32_t* chosen = c->kit_slots + q0;
+    {
+        FillScope fills(true);
+        HIPCHK(packed_fill(d, 0, (size_t)qn * MAX_T * 8, c->stream));
+        HIPCHK(packed_fill(d_first, 0xFF, (size_t)qn * MAX_T * 8, c->stream));
+        HIPCHK(packed_fill_flush(c->stream));
+    }
+    const uint32_t blocks = std::min<uint32_t>((j.per + 255) / 256, span_reads ? 64 : 1024);
+    hipLaunchKernelGGL(k_vote, dim3(blocks, qn), dim3(256), 0, c->stream, kd->kit, c->recs, rn, d, d_first, span_reads);
+    hipLaunchKernelGGL(k_pick_kit, dim3(qn), dim3(64), 0, c->stream, kd->kit, d, d_first, chosen);
+    c->packed.kit_slot_dev = chosen; c->packed.kit_slot_span = span_reads * 2u;
+    return scan_resident_impl(c, kit, &view, ScanPass::resume(RESUME_KIT_ON_DEVICE).keeping_counts(q0 > 0).deferring_counts(j.filter));
+}
+
+extern "C" int qcat_scan_resident_batches(qcat_ctx* c, const qcat_kit* ckit, const qcat_batch* b, uint32_t batch_reads, uint32_t flags) {
+    int rc = resident_batches_check(c, ckit, b, flags);
+    if (rc) return rc;
+    if (!flags) return qcat_scan_resident(c, ckit, b);                  // the same launches, the same records
+    qcat_kit* kit = const_cast<qcat_kit*>(ckit);
+    const DevKit& hk = kit->hk.dk;
+    if (!b->n_reads) {                                                  // nobody votes, nothing to filter: zero batches
+        if ((rc = scan_resident_impl(c, kit, b, ScanPass::plain()))) return rc;
+        if (flags & QCAT_RESIDENT_KIT_AUTO) c->auto_batches = 0;
+        return 0;
+    }
+    if (b->true_len) return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: the batch holds read windows, not whole reads");
+    ResidentBatchesJob j{};
+    if ((rc = resident_batches_plan(hk, b, batch_reads, flags, j))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    KitOnDevice* kd = nullptr;
+    if ((rc = kit_on_device(kit, c->device, &kd))) return rc;
+    // a failure below leaves no scan behind: no records to fetch or to partition, no slots
+    auto failed = [&](int code) { c->res_first = 0; c->last_kit = nullptr; c->last_n_reads = 0; c->auto_batches = -1; return code; };
+    if (j.kit_auto) {
+        // the records of every chunk in read order in c->results: sized for the whole batch first, so that no chunk's scan moves it
+        if ((rc = grow(c->results, (size_t)j.n))) return failed(rc);
+        if ((rc = grow(c->kit_slots, (size_t)j.n_batches))) return failed(rc);
+        for (uint32_t q0 = 0; q0 < j.n_batches; q0 += j.chunk_batches)
+            if ((rc = resident_vote_chunk(c, kit, kd, b, j, q0, std::min(j.chunk_batches, j.n_batches - q0)))) return failed(rc);
+        c->res_first = 0;
+    } else if ((rc = scan_resident_impl(c, kit, b, ScanPass::plain().deferring_counts(true)))) return failed(rc);
+    if (j.filter) {
+        // behind k_finalize and the interior scan, in front of the counts: the counts are those of the filtered records
+        const KitPtrs kp{kd->kit, kd->codes, kd->ids, kd->tables};
+        if ((rc = filter_run(c, hk, kp, c->results, j.n, j.per))) return failed(rc);
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((j.n + 255) / 256, hk.n_buckets > 2048 ? 512 : 1024);
+        hipLaunchKernelGGL(k_count, dim3(blocks), dim3(256), 0, c->stream, kp, (const qcat_result*)c->results.get(), (const uint64_t*)b->offsets,
+                           (const uint32_t*)nullptr, j.n, c->counts.get());
+        mark(c, "k_count");
+        if (hipGetLastError() != hipSuccess) return failed(set_err(QCAT_ERR_DEVICE, "qcat_scan_resident_batches: launch of k_count failed"));
+    }
+    c->last_kit = kit; c->last_n_reads = j.n; c->last_buckets = hk.n_buckets;
+    c->auto_batches = j.kit_auto ? (int64_t)j.n_batches : -1;
+    return 0;
+}
+
+extern "C" int qcat_ctx_fetch_kit_slots(qcat_ctx* c, int32_t* slots, uint32_t n_batches) {
+    if (!c || (!slots && n_batches)) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_kit_slots: null argument");
+    if (c->auto_batches < 0)
+        return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_kit_slots: this context's latest scan was no qcat_scan_resident_batches with QCAT_RESIDENT_KIT_AUTO");
+    if ((int64_t)n_batches != c->auto_batches) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_kit_slots: n_batches does not match the latest scan");
+    HIPCHK(hipSetDevice(c->device));
+    if (n_batches) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(slots, c->kit_slots, (size_t)n_batches * 4, hipMemcpyDeviceToHost, c->stream));
+    return stream_done(c, "qcat_ctx_fetch_kit_slots");
 }
 
 extern "C" int qcat_scan_batch(qcat_ctx* c, const qcat_kit* kit,

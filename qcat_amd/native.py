@@ -36,6 +36,7 @@ def get_r1_rule():
     return _r1_rule[0]
 MODE_EPI2ME, MODE_DUAL, MODE_SIMPLE = 0, 1, 2
 ENDS_5P, ENDS_BOTH = 1, 3
+RESIDENT_KIT_AUTO, RESIDENT_FILTER_BARCODES = 1, 2          # flags of qcat_scan_resident_batches
 MAX_TEMPLATES = 16
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -391,6 +392,9 @@ class HipLibrary(object):
             "qcat_batch_devptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
             "qcat_synth_read": (C.c_int64, [vp, C.POINTER(SynthParams), C.c_uint64, vp, C.c_uint64]),
             "qcat_scan_resident": (C.c_int, [vp, vp, vp]),
+            "qcat_scan_resident_batches": (C.c_int, [vp, vp, vp, u32, u32]),
+            "qcat_ctx_fetch_kit_slots": (C.c_int, [vp, vp, u32]),
+            "qcat_filter_barcodes": (C.c_int, [vp, vp, vp, u32, u32]),
             "qcat_ctx_synchronize": (C.c_int, [vp]),
             "qcat_ctx_fetch_results": (C.c_int, [vp, vp, u32]),
             "qcat_ctx_fetch_counts": (C.c_int, [vp, vp, i32]),
@@ -777,10 +781,49 @@ class NativeContext(object):
         self.hip.check(self.hip.lib.qcat_ctx_fetch_counts(self.handle, counts.ctypes.data, nb))
         return recs, counts
 
+    def scan_resident_batches(self, kit, batch, batch_reads, kit_auto=False, filter_barcodes=False, fetch=True):
+        """qcat_scan_resident_batches: :meth:`scan_resident` with the reference driver's per-batch semantics -- reads
+        ``[q * batch_reads, (q + 1) * batch_reads)`` are batch q (0: the whole resident batch is one batch).  ``kit_auto``: ``kit``
+        holds the templates of every kit and each batch votes for one on the device; ``filter_barcodes``: the driver's
+        --filter-barcodes per batch, on the device.  Returns (records, counts, voted kit slot per batch -- None without
+        ``kit_auto``), or None with ``fetch=False``: everything stays on the device and the next :meth:`partition` of ``batch``
+        follows this scan."""
+        handle = kit.handle
+        flags = (RESIDENT_KIT_AUTO if kit_auto else 0) | (RESIDENT_FILTER_BARCODES if filter_barcodes else 0)
+        self._resident_scan = None
+        self.hip.check(self.hip.lib.qcat_scan_resident_batches(self.handle, handle, batch.handle, int(batch_reads), flags))
+        self._resident_scan = (kit, handle, batch)
+        if not fetch:
+            return None
+        n = batch.n_reads
+        recs = np.zeros(n, dtype=RESULT_DTYPE)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_results(self.handle, recs.ctypes.data, n))
+        nb = self.hip.lib.qcat_kit_count_buckets(handle)
+        counts = np.zeros(nb, dtype=np.int64)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_counts(self.handle, counts.ctypes.data, nb))
+        return recs, counts, (self.fetch_kit_slots(n, batch_reads) if kit_auto else None)
+
+    def fetch_kit_slots(self, n_reads, batch_reads):
+        """qcat_ctx_fetch_kit_slots: the kit slot every batch of the latest kit-auto :meth:`scan_resident_batches` voted for
+        (int32, one per batch; RuntimeError when the latest scan did not vote)"""
+        per = n_reads if (batch_reads == 0 or batch_reads >= n_reads) else int(batch_reads)
+        nb = (n_reads + per - 1) // per if n_reads else 0
+        slots = np.full(nb, -1, dtype=np.int32)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_kit_slots(self.handle, slots.ctypes.data if nb else None, nb))
+        return slots
+
+    def filter_barcodes(self, kit, records, batch_reads):
+        """qcat_filter_barcodes: the driver's --filter-barcodes per batch of ``batch_reads`` records (0: one batch) on records
+        the caller holds -- a filtered copy; the kernels are those of :meth:`scan_resident_batches`."""
+        out = np.array(records, dtype=RESULT_DTYPE, copy=True, order="C")
+        self.hip.check(self.hip.lib.qcat_filter_barcodes(self.handle, kit.handle, out.ctypes.data if len(out) else None, len(out),
+                                                         int(batch_reads)))
+        return out
+
     def partition(self, kit, batch, records=None):
         """qcat_batch_partition: the reads of ``batch`` grouped by barcode -- a :class:`Partition`.  ``records``: a RESULT_DTYPE
-        array with one record per read, or None for the records of this context's latest :meth:`scan_resident` (of ``batch``
-        with ``kit``)."""
+        array with one record per read, or None for the records of this context's latest :meth:`scan_resident` or
+        :meth:`scan_resident_batches` (of ``batch`` with ``kit``)."""
         handle = kit.handle
         last = getattr(self, "_resident_scan", None)
         if records is None and last is not None and last[0] is kit:

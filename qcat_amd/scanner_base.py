@@ -457,14 +457,37 @@ class BarcodeScanner(object):
         kits = sorted(set(l.kit for l in self.layouts))
         if self._native_mode != "simple" and len(kits) != 1:
             raise ValueError("demux_batch needs a scanner with a fixed kit: the partition follows ONE resident scan, which has one "
-                             "kit, and kit auto votes per batch (this scanner holds %d kits)" % len(kits))
+                             "kit, and kit auto votes per batch (this scanner holds %d kits; demux_batches votes per batch)" % len(kits))
         kit = self._native_kit(self.layouts, qcat_config, native.ENDS_BOTH, min_read_length=min_read_length, trim=trim)
+        return self._demux_resident(kit, read_sequences, read_qualities,
+                                    lambda ctx, batch: ctx.scan_resident(kit, batch, fetch=False))
+
+    def demux_batches(self, read_sequences, batch_size=4000, trim=False, min_read_length=0, qcat_config=None, read_qualities=None):
+        """The reference driver's loop (``qcat/cli.py:500``: ``detect_barcode_batch`` per ``batch_size`` reads, then trimming,
+        the minimum-length filter and the per-barcode writers) for reads in device memory: ONE upload, one resident scan with
+        the driver's per-batch semantics (qcat_scan_resident_batches), the stable partition.  A scanner that holds several
+        kits votes a kit per batch on the device (``qcat/scanner_base.py:662-678``); a scanner made with
+        ``enable_filter_barcodes`` filters every batch there (``:690-712``); ``scan_middle_adapter`` is part of the kit.
+        Returns what :meth:`demux_batch` returns; under a kit vote the bins are the Barcode ids of all kits, one bin per id."""
+        if qcat_config is None:
+            qcat_config = config.qcatConfig()
+        if not self.layouts and self._native_mode != "simple":
+            raise IndexError("list index out of range")
+        kit_auto = self._native_mode != "simple" and len(set(l.kit for l in self.layouts)) > 1
+        kit = self._native_kit(self.layouts, qcat_config, native.ENDS_BOTH, min_read_length=min_read_length, trim=trim)
+        return self._demux_resident(kit, read_sequences, read_qualities,
+                                    lambda ctx, batch: ctx.scan_resident_batches(kit, batch, int(batch_size), kit_auto=kit_auto,
+                                                                                 filter_barcodes=bool(self.enable_filter_barcodes),
+                                                                                 fetch=False))
+
+    def _demux_resident(self, kit, read_sequences, read_qualities, scan):
+        """upload, ``scan(ctx, batch)``, partition, and the bins as :meth:`demux_batch` returns them"""
         ctx = self._context()
         bases, offsets = native.pack_reads(read_sequences)
         quals = None if read_qualities is None else native.pack_qualities(read_qualities, offsets)
         batch = native.ResidentBatch.upload(ctx, bases, offsets, quals)
         try:
-            ctx.scan_resident(kit, batch, fetch=False)
+            scan(ctx, batch)
             part = ctx.partition(kit, batch)
         finally:
             batch.destroy()
