@@ -35,8 +35,7 @@
 #include <immintrin.h>
 #endif
 
-// (struct qk::FqRec -- title: offset of the byte after '@'; seq, qual: offsets of the sequence / quality lines; title_len
-//  after rstrip; seq_len == quality length -- is declared beside ReadView in qcat_hip.hip, where the pipeline reads it)
+// (struct qk::FqRec, one record of the file, is declared in pipeline.h beside ReadView, the pipeline's view of the reads)
 
 struct qcat_fastq {
     int fd = -1;

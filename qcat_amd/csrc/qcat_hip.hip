@@ -40,7 +40,7 @@
 #include "kernels_partition.inc"
 #include "kernels_filter.inc"
 #include "static_registry.inc"
-#include "host_pipeline.inc"
+#include "pipeline.h"
 
 using namespace qk;
 
@@ -146,7 +146,7 @@ extern "C" int qcat_device_count(void) {
 }
 
 // NUMA node of a device's PCI function (sysfs), -1 when unknown: the rank launcher (qcat_amd/parallel.py) keeps a
-// rank's host threads -- the compaction pool of host_pipeline.inc -- on the node its GPU hangs off
+// rank's host threads -- the compaction pool of pipeline_core.h -- on the node its GPU hangs off
 extern "C" int qcat_device_numa_node(int device) {
     char bdf[64] = {0};
     if (device < 0 || device >= qcat_device_count()) return -1;
@@ -446,6 +446,9 @@ static int kit_on_device(qcat_kit* k, int device, KitOnDevice** out) {
 // the interior scan of --detect-middle on a resident batch: its scratch (MiddleScratch) and launch sequence
 #include "middle_host.inc"
 
+// the device work of a host-buffer call as a captured graph: ApiGraph, api_graph_run
+#include "api_graph.inc"
+
 // ------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------
@@ -470,7 +473,7 @@ struct qcat_ctx {
                                                             // memory are one DMA each; into the caller's pageable arrays the runtime stages
                                                             // every one through a copy kernel and a host memcpy (round 6: five of them were
                                                             // 100 us of a 4000-read kit-auto call)
-    HostPipeline* pipe = nullptr;                  // chunked host-buffer scans (host_pipeline.inc), created on first use
+    HostPipeline* pipe = nullptr;                  // chunked host-buffer scans (pipeline.h, pipeline_host.inc), created on first use
     std::vector<qcat_ctx*> helpers;                // contexts of the kit-auto file loop's other workers (fastq_host.inc), created on first use
     PackedScratch packed;
     MiddleScratch middle;                          // the interior scan of --detect-middle (middle_host.inc)
@@ -487,16 +490,10 @@ struct qcat_ctx {
     // reused -- a 4000-read batch of the reference driver's call shape spent a third of its call in six hipMalloc / hipFree
     DevBuf<uint8_t> hb_bases;
     DevBuf<uint64_t> hb_offsets; DevBuf<uint32_t> hb_len;
-    DevBuf<uint8_t> vote_buf;                      // per batch of a kit vote: MAX_T counters, MAX_T first voters, then one chosen slot each (+ 16 bytes)
-    // the device work of a kit-auto host-buffer call as a captured graph (scan_batch_auto_impl): two dozen launches (round 5: ~45 on
-    // twelve streams) replayed by one hipGraphLaunch when a call has the shape of the one before it
-    struct ApiGraph {
-        hipGraphExec_t exec = nullptr;
-        uint64_t kit = 0, n_bases = 0, gen = 0; uint32_t n_reads = 0, batch_reads = 0;             // what `exec` was captured for
-        uint64_t prev_kit = 0, prev_bases = 0, prev_gen = 0; uint32_t prev_reads = 0, prev_batch = 0;   // the shape of the last call
-        int failures = 0;                                                         // captures that did not work out (two: never again)
-        uint64_t replays = 0;
-    } api_graph, scan_graph;                       // kit-auto calls (scan_batch_auto_impl); calls with a named kit (qcat_scan_batch, round 5)
+    DevBuf<uint8_t> vote_buf;                      // the block of a kit vote (vote_host.inc: VoteBuf)
+    // the device work of a host-buffer call as a captured graph (api_graph.inc): kit-auto calls (scan_batch_auto_impl); calls
+    // with a named kit (qcat_scan_batch, round 5)
+    ApiGraph api_graph, scan_graph;
     // the handful-of-reads path (kernels_tiny.inc): per read end the templates' (raw, end) and the barcodes' raw scores
     DevBuf<int32_t> tiny_tpl; DevBuf<int16_t> tiny_sc;
     uint32_t last_tiny_ends = 0;                   // read ends the last scan put on that path (0: another path)
@@ -1034,6 +1031,9 @@ extern "C" int qcat_ctx_last_timing(qcat_ctx* c, const char** names, float* ms, 
 #include "batch_host.inc"
 // --filter-barcodes on the device: filter_run for the records of a scan, qcat_filter_barcodes for records of a caller
 #include "filter_host.inc"
+// the kit vote: VoteBuf and vote_enqueue, and the entry points that vote -- qcat_detect_kit, the kit-auto host-buffer calls,
+// qcat_scan_resident_batches
+#include "vote_host.inc"
 
 // ------------------------------------------------------------------------------------------
 // host-buffer entry points
@@ -1059,269 +1059,8 @@ static void fill_trace(const HostKit& hk, const EndRec& r, const int32_t* tplraw
     }
 }
 
-// qcat_scan_batch over host buffers as a chunked pipeline (host_pipeline.inc).  Returns 1 when the batch
-// does not qualify (small, --detect-middle, disabled) and the caller should take the one-shot path.
-// where the reads of a host batch lie: concatenated (bases + offsets, the form of qcat_scan_batch) or scattered through a
-// mapped FASTQ file (one FqRec per read, fastq_host.inc) -- the pipeline only ever reads head and tail of a read in place
-namespace qk { struct FqRec { uint64_t title, seq, qual; uint32_t title_len, seq_len; }; }
-struct ReadView {
-    const uint8_t* bases;
-    const uint64_t* offsets;           // concatenated form (recs == nullptr)
-    const qk::FqRec* recs;             // FASTQ form: bases = the mapping, read r = recs[r]
-    inline uint64_t start(uint32_t r) const { return recs ? recs[r].seq : offsets[r]; }
-    inline uint64_t len(uint32_t r) const { return recs ? (uint64_t)recs[r].seq_len : offsets[r + 1] - offsets[r]; }
-};
-
-static int scan_batch_pipelined(qcat_ctx* c, qcat_kit* kit, const ReadView& rv,
-                                uint32_t n_reads, qcat_result* out, int64_t* counts) {
-    const DevKit& hk = kit->hk.dk;
-    const uint8_t* bases = rv.bases;
-    if (hk.scan_middle || n_reads < 32768 || opt_on(QO_FULL_UPLOAD) || opt_on(QO_NO_PIPELINE)) return 1;
-    if (!rv.recs) {
-        if (!bases && rv.offsets[n_reads] > 0) return set_err(QCAT_ERR_ARG, "qcat_scan_batch: null argument");
-        if (rv.offsets[0] != 0) return set_err(QCAT_ERR_ARG, "offsets[0] must be 0");
-    }
-    HIPCHK(hipSetDevice(c->device));
-    const uint64_t n = (uint64_t)hk.max_align;
-    const bool both = hk.ends == QCAT_ENDS_BOTH;
-    const uint64_t keep = both ? 2 * n : n;
-    const auto t_entry = std::chrono::steady_clock::now();
-    if (!c->pipe) {
-        c->pipe = new HostPipeline();
-        c->pipe->pool = new HostPool(host_threads() - 1);
-        // the copy stream gets the highest priority: the runtime multiplexes streams of one priority onto a few
-        // hardware queues, and a copy queued behind a 20 ms persistent barcode kernel of a side stream would
-        // not start before that kernel ends (measured: no copy/compute overlap at all on a default stream)
-        int prio_low = 0, prio_high = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-        HIPCHK(hipStreamCreateWithPriority(&c->pipe->copy, hipStreamNonBlocking, prio_high));
-        for (PipeStage& st : c->pipe->st) {
-            HIPCHK(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&st.scanned, hipEventDisableTiming));
-        }
-    }
-    HostPipeline* p = c->pipe;
-    // chunks of 256 k .. 1 M reads (a quarter of the batch): big enough to fill the chip (1 000+ tiles of 128
-    // alignments), small enough that the first chunk's compaction and the last chunk's scan -- the only
-    // stages nothing overlaps -- are a small part of the call
-    const QOptVal ce = qopt_get(QO_PIPELINE_CHUNK);
-    // (heavier per-chunk launches lose less to the tails of the persistent barcode kernels: large batches take 1 M-read chunks)
-    // (a chunk costs ~0.3 ms of host time in launches and copies whatever its size: 1 M reads of a small kit run
-    // 166 M reads/s in four chunks, 137 M in eight, 97 M in sixteen)
-    // (reads of a FASTQ mapping: a one-shot process pays for every pinned byte it sets up, 0.2 ms per MiB, and the host side
-    // bounds the rate anyway -- 256 k-read chunks)
-    const uint32_t chunk = ce ? (uint32_t)std::max(4096, atoi(ce))
-                              : (rv.recs ? 262144u : std::min<uint32_t>(1048576u, std::max<uint32_t>(262144u, n_reads / 4u)));
-    // chunk boundaries: the first and the last chunk are a third of the others -- nothing overlaps the first chunk's
-    // compaction and the last chunk's upload + scan + download
-    std::vector<uint32_t> cuts;
-    cuts.push_back(0);
-    if (!ce && n_reads > 2 * chunk) {
-        const uint32_t edge = chunk / 3, mid = n_reads - 2 * edge, m = (mid + chunk - 1) / chunk;
-        for (uint32_t q = 0; q <= m; ++q) cuts.push_back(edge + (uint32_t)((uint64_t)mid * q / m));    // equal middle chunks
-        cuts.push_back(n_reads);
-    } else {
-        for (uint32_t pos = chunk; pos < n_reads; pos += chunk) cuts.push_back(pos);
-        cuts.push_back(n_reads);
-    }
-    const uint32_t n_chunks = (uint32_t)cuts.size() - 1;
-    // staging for the LARGEST chunk of this call, and for the second slot only when there is a second chunk (round 6: a segment of
-    // the file loop is one chunk of 40-180 k reads -- sizing both slots for 256 k reads pinned 157 MB, 0.2 ms per MiB, in front
-    // of the first segment's scan: 42 ms of a 160 ms run); a later, bigger call grows them with headroom
-    uint32_t largest = 0;
-    for (uint32_t q = 0; q < n_chunks; ++q) largest = std::max(largest, cuts[q + 1] - cuts[q]);
-    for (PipeStage& st : p->st) {
-        if (&st != &p->st[0] && n_chunks < 2) break;
-        size_t need_reads = (size_t)largest + 1, need_bases = (size_t)largest * keep + 2 * BATCH_SLACK;
-        // (the arrays of a group grow together: the smallest capacity stands for the group, 0 after an allocation that failed)
-        const size_t cap_reads = std::min({st.pin_offsets.cap(), st.pin_len.cap(), st.pin_results.cap(), st.dev_offsets.cap(), st.dev_len.cap()});
-        const size_t cap_bases = std::min(st.pin_bases.cap(), st.dev_bases_alloc.cap());
-        if (need_reads > cap_reads && cap_reads) need_reads = std::min<size_t>((size_t)chunk + 1, need_reads + need_reads / 2);
-        if (need_bases > cap_bases && cap_bases) need_bases = std::min<size_t>((size_t)chunk * keep + 2 * BATCH_SLACK, need_bases + need_bases / 2);
-        HIPCHK(st.pin_offsets.ensure(need_reads));
-        HIPCHK(st.pin_len.ensure(need_reads));
-        HIPCHK(st.pin_results.ensure(need_reads));
-        HIPCHK(st.dev_offsets.ensure(need_reads));
-        HIPCHK(st.dev_len.ensure(need_reads));
-        HIPCHK(st.pin_bases.ensure(need_bases));
-        HIPCHK(st.dev_bases_alloc.ensure(need_bases));
-    }
-    struct TimingOff {                                   // per-kernel events describe one scan, not a chunk train
-        qcat_ctx* c; bool was;
-        explicit TimingOff(qcat_ctx* c_) : c(c_), was(c_->timing) { c->timing = false; }
-        ~TimingOff() { c->timing = was; }
-    } timing_off(c);
-    int rc = 0;
-    const bool trace = opt_on(QO_PIPELINE_TRACE);
-    double t_wait = 0, t_prefix = 0, t_compact = 0, t_enqueue = 0;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
-    // a slot's records go to the caller's array once its scan is known to be done
-    auto flush_results = [&](PipeStage& st) {
-        if (!st.res_count) return;
-        const uint32_t cnt = st.res_count, first = st.res_first;
-        const int parts = (int)std::min<uint32_t>(p->pool->size(), std::max<uint32_t>(1u, cnt / 65536u));
-        const uint32_t per = (cnt + parts - 1) / parts;
-        p->pool->run(parts, [&](int part) {
-            const uint32_t a = std::min<uint32_t>(cnt, (uint32_t)part * per), b2 = std::min<uint32_t>(cnt, a + per);
-            if (b2 > a) memcpy(out + first + a, st.pin_results + a, (size_t)(b2 - a) * sizeof(qcat_result));
-        });
-        st.res_count = 0;
-    };
-    for (PipeStage& st : p->st) st.res_count = 0;
-    for (uint32_t ci = 0; ci < n_chunks && !rc; ++ci) {
-        PipeStage& st = p->st[ci & 1];
-        double t0 = now();
-        const uint32_t r0 = cuts[ci], nr = cuts[ci + 1] - r0;
-        if (ci >= 2) HIPCHK(hipEventSynchronize(st.copied));          // this slot's pinned staging has been read
-        t_wait += now() - t0; t0 = now();
-        // offsets + real lengths of the compacted chunk: per-part sums in parallel, a serial scan over the parts,
-        // then every part writes its offsets and copies its reads
-        const int parts = (int)std::min<uint32_t>(std::min<uint32_t>(p->pool->size() * 4, 256u), std::max<uint32_t>(1u, nr / 4096u));
-        const uint32_t per = (nr + parts - 1) / parts;
-        uint64_t part_total[256];
-        int part_err[256];
-        p->pool->run(parts, [&](int part) {
-            const uint32_t a = std::min<uint32_t>(nr, (uint32_t)part * per), b2 = std::min<uint32_t>(nr, a + per);
-            uint64_t sum = 0; int err = 0;
-            for (uint32_t r = a; r < b2; ++r) {
-                if (!rv.recs && rv.offsets[r0 + r + 1] < rv.offsets[r0 + r]) { err = 1; break; }
-                const uint64_t len = rv.len(r0 + r);
-                if (len > 0xFFFFFFFFull) { err = 2; break; }
-                sum += len <= keep ? len : keep;
-            }
-            part_total[part] = sum; part_err[part] = err;
-        });
-        uint64_t total = 0;
-        for (int q = 0; q < parts; ++q) {
-            if (part_err[q] == 1) rc = set_err(QCAT_ERR_ARG, "offsets must be non-decreasing");
-            else if (part_err[q] == 2) rc = set_err(QCAT_ERR_UNSUPPORTED, "read longer than 4 Gb");
-            const uint64_t t = part_total[q]; part_total[q] = total; total += t;
-        }
-        if (rc) break;
-        st.pin_offsets[0] = 0;
-        t_prefix += now() - t0; t0 = now();
-        p->pool->run(parts, [&](int part) {
-            const uint32_t a = std::min<uint32_t>(nr, (uint32_t)part * per), b2 = std::min<uint32_t>(nr, a + per);
-            uint64_t pos = part_total[part];
-            constexpr uint32_t AHEAD = 12;                           // reads: the windows are 150 B out of every ~700, each a cache
-            for (uint32_t r = a; r < b2; ++r) {                      // miss the hardware prefetcher does not see coming
-                if (r + AHEAD < b2) {
-                    const uint64_t px = rv.start(r0 + r + AHEAD), py = px + rv.len(r0 + r + AHEAD);
-                    const uint8_t* ps = bases + px;
-                    __builtin_prefetch(ps, 0, 0); __builtin_prefetch(ps + 64, 0, 0); __builtin_prefetch(ps + 128, 0, 0);
-                    if (both && py - px > keep) {
-                        const uint8_t* pt = bases + py - n;
-                        __builtin_prefetch(pt, 0, 0); __builtin_prefetch(pt + 64, 0, 0); __builtin_prefetch(pt + 128, 0, 0);
-                    }
-                }
-                const uint64_t x = rv.start(r0 + r);
-                const uint64_t len = rv.len(r0 + r);
-                const uint8_t* src = bases + x;
-                uint8_t* dst = st.pin_bases + pos;
-                st.pin_len[r] = (uint32_t)len;
-                if (len <= keep) { memcpy(dst, src, len); pos += len; }
-                else { memcpy(dst, src, n); if (both) memcpy(dst + n, src + len - n, n); pos += keep; }
-                st.pin_offsets[r + 1] = pos;
-            }
-        });
-        t_compact += now() - t0; t0 = now();
-        // this slot's device buffers are free again once the scan of chunk ci - 2 is done: waited for on the HOST, so
-        // that the copy stream never holds a barrier packet behind which its copies would queue up
-        if (ci >= 2) { HIPCHK(hipEventSynchronize(st.scanned)); flush_results(st); }
-        if (total) HIPCHK(hipMemcpyAsync(st.dev_bases_alloc + BATCH_SLACK, st.pin_bases, total, hipMemcpyHostToDevice, p->copy));
-        HIPCHK(hipMemcpyAsync(st.dev_offsets, st.pin_offsets, ((size_t)nr + 1) * 8, hipMemcpyHostToDevice, p->copy));
-        HIPCHK(hipMemcpyAsync(st.dev_len, st.pin_len, (size_t)nr * 4, hipMemcpyHostToDevice, p->copy));
-        HIPCHK(hipEventRecord(st.copied, p->copy));
-        HIPCHK(hipStreamWaitEvent(c->stream, st.copied, 0));
-        // the chunk as a resident batch (no ownership); its bases begin behind the front slack of the stage's allocation
-        uint8_t* const chunk_bases = st.dev_bases_alloc + BATCH_SLACK;
-        const qcat_batch view = batch_view(c->device, nr, total, chunk_bases, st.dev_offsets, st.dev_len);
-        rc = scan_resident_impl(c, kit, &view, ScanPass::plain().keeping_counts(ci > 0));
-        if (rc) break;
-        HIPCHK(hipMemcpyAsync(st.pin_results, c->results, (size_t)nr * sizeof(qcat_result), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipEventRecord(st.scanned, c->stream));
-        st.res_first = r0; st.res_count = nr;
-        t_enqueue += now() - t0;
-    }
-    const double t_loop = now();
-    hipError_t es = hipStreamSynchronize(c->stream);
-    hipError_t ec = hipStreamSynchronize(p->copy);
-    if (trace)
-        fprintf(stderr, "[qcat pipeline] %u reads, %u chunks, %u threads: set-up (pool, pinned and device staging) %.2f ms, staging wait %.2f ms, "
-                        "prefix %.2f, compaction %.2f, enqueue %.2f, drain %.2f, total so far %.2f ms\n", n_reads, n_chunks, p->pool->size(),
-                t_begin - std::chrono::duration<double, std::milli>(t_entry.time_since_epoch()).count(), t_wait, t_prefix, t_compact, t_enqueue,
-                now() - t_loop, now() - t_begin);
-    c->last_n_reads = 0;                                 // the context's result buffer holds the last chunk only
-    c->last_kit = nullptr;
-    if (rc) return rc;
-    if (es != hipSuccess || ec != hipSuccess)
-        return set_err(QCAT_ERR_DEVICE, std::string("qcat_scan_batch: ") + hipGetErrorString(es != hipSuccess ? es : ec));
-    for (PipeStage& st : p->st) flush_results(st);
-    if (counts) {
-        std::vector<int64_t> tmp((size_t)hk.n_buckets);
-        c->last_buckets = hk.n_buckets;
-        if ((rc = qcat_ctx_fetch_counts(c, tmp.data(), hk.n_buckets))) return rc;
-        for (size_t i = 0; i < tmp.size(); ++i) counts[i] += tmp[i];
-    }
-    return 0;
-}
-
-// The device work of a host-buffer call -- everything between the upload and the download -- launched kernel by kernel
-// (`enqueue`) or replayed as ONE graph.  A call shaped like the one before it (same kit, read count, compacted bases; nothing
-// reallocated in between) replays: the launches take no arguments from the host but buffer addresses and sizes, every
-// decision that depends on the data (kit vote, job plan, cursors) is made on the device.  The second such call captures
-// (hipStreamBeginCapture, thread-local mode; the side streams join the capture through fork_join's events), later ones
-// replay (`prep`: host-side state a replay needs as well).  QCAT_HIP_NO_GRAPH=1: always launch kernel by kernel.  Timed
-// contexts and the diagnostic switches (they synchronise inside the scan) never capture.  A failure drains the stream before
-// it returns (the upload may still be reading the pinned staging).
-template <class Enqueue, class Prep>
-static int api_graph_run(qcat_ctx* c, qcat_ctx::ApiGraph& G, qcat_kit* kit, KitOnDevice* kd, const qcat_batch* b, uint32_t batch_reads,
-                         Enqueue enqueue, Prep prep) {
-    const uint32_t n_reads = b->n_reads;
-    auto drained = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
-    static const QcatOpt no_capture[] = {QO_NO_GRAPH, QO_DEBUG_VOTE, QO_BS_TRACE, QO_DEBUG_BINS, QO_DEBUG_REDO};
-    bool graph_ok = !c->timing && G.failures < 2 && !b->owned() && !kit->hk.dk.scan_middle && !opt_on(QO_FULL_UPLOAD);      // (whole reads -- --detect-middle -- never replay)
-    for (QcatOpt o : no_capture) if (opt_on(o)) graph_ok = false;
-    const uint64_t gen_before = g_alloc_gen.load();
-    bool done = false;
-    int rc = 0;
-    if (graph_ok && G.exec && G.kit == kit->serial && G.n_reads == n_reads && G.n_bases == b->n_bases && G.gen == gen_before && G.batch_reads == batch_reads) {
-        prep();
-        g_jit = kd;
-        HIPCHK_DRAIN(c->stream, hipGraphLaunch(G.exec, c->stream));
-        ++G.replays;
-        done = true;
-    } else if (graph_ok && G.prev_kit == kit->serial && G.prev_reads == n_reads && G.prev_bases == b->n_bases && G.prev_gen == gen_before && G.prev_batch == batch_reads) {
-        if (G.exec) { (void)hipGraphExecDestroy(G.exec); G.exec = nullptr; }
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int erc = enqueue();
-            const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
-            const bool captured = erc == 0 && ee == hipSuccess && graph != nullptr;
-            const bool moved = g_alloc_gen.load() != gen_before;     // (some context allocated meanwhile: not this call's failure)
-            if (captured && !moved && hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                G.kit = kit->serial; G.n_reads = n_reads; G.n_bases = b->n_bases; G.gen = gen_before; G.batch_reads = batch_reads;
-                if (hipGraphLaunch(G.exec, c->stream) == hipSuccess) done = true;
-            }
-            if (graph) (void)hipGraphDestroy(graph);
-            if (!done && !(captured && moved)) {
-                ++G.failures;
-                (void)hipGetLastError();
-                (void)hipStreamSynchronize(c->stream);
-                packed_streams_reset(&c->packed);                // (fresh side streams: the old ones may still think they capture)
-            }
-        } else ++G.failures;
-        if (!done) {                                             // (nothing of the capture ran: the plain launches below do the work)
-            (void)hipGetLastError();
-            if (G.exec) { (void)hipGraphExecDestroy(G.exec); G.exec = nullptr; }
-            FillScope drop(false);                                 // (whatever the capture queued and did not flush)
-        }
-    }
-    if (!done && (rc = enqueue())) return drained(rc);
-    G.prev_kit = kit->serial; G.prev_reads = n_reads; G.prev_bases = b->n_bases; G.prev_gen = g_alloc_gen.load(); G.prev_batch = batch_reads;
-    return 0;
-}
+// qcat_scan_batch over host buffers as a chunked pipeline (pipeline.h): scan_batch_pipelined
+#include "pipeline_host.inc"
 
 // (ptrs / lens: the reads as one pointer and one length each instead of bases / offsets -- the file loops' one-shot path)
 static int scan_debug_impl(qcat_ctx* c, const qcat_kit* ckit,
@@ -1343,7 +1082,8 @@ static int scan_debug_impl(qcat_ctx* c, const qcat_kit* ckit,
         // replay them as a graph, like the kit-auto calls (api_graph_run)
         KitOnDevice* kd = nullptr;
         rc = kit_on_device(kit, c->device, &kd);
-        if (!rc) rc = api_graph_run(c, c->scan_graph, kit, kd, b, 0, [&] { return scan_resident_impl(c, kit, b, ScanPass::plain()); }, [] {});
+        if (!rc) rc = api_graph_run(c->stream, c->timing, &c->packed, c->scan_graph, kit, kd, b, 0,
+                                    [&] { return scan_resident_impl(c, kit, b, ScanPass::plain()); }, [] {});
         else (void)hipStreamSynchronize(c->stream);
         if (!rc) { c->last_n_reads = n_reads; c->last_buckets = kit->hk.dk.n_buckets; }      // (a replay does not pass through scan_resident_impl)
     } else rc = scan_resident_impl(c, kit, b, debug ? ScanPass::debug(bc_rows ? row_stride : 0) : ScanPass::plain());
@@ -1372,295 +1112,6 @@ extern "C" int qcat_scan_debug(qcat_ctx* c, const qcat_kit* ckit,
                                qcat_end_trace* traces, int16_t* bc_rows, uint32_t row_stride) {
     if (!offsets) return set_err(QCAT_ERR_ARG, "null argument");
     return scan_debug_impl(c, ckit, bases, offsets, nullptr, nullptr, n_reads, out, counts, traces, bc_rows, row_stride);
-}
-
-// the vote's device buffer for nb batches: votes [nb][MAX_T], first voters [nb][MAX_T], chosen slots [nb]
-static int vote_buffer(qcat_ctx* c, size_t nb) {
-    HIPCHK(c->vote_buf.ensure(nb * (2 * MAX_T * 8 + 4) + 16));
-    return 0;
-}
-
-// adapter-only pass over a resident batch + k_vote: per-template votes / first voting read (host arrays of MAX_T)
-static int vote_resident(qcat_ctx* c, qcat_kit* kit, const qcat_batch* b, unsigned long long* hv, unsigned long long* hf) {
-    for (int t = 0; t < MAX_T; ++t) { hv[t] = 0; hf[t] = ~0ull; }
-    int rc = scan_resident_impl(c, kit, b, ScanPass::vote());
-    // (a failed step drains the stream before it returns: the caller's upload may still be reading the pinned staging)
-    auto drained = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
-    if (rc) return drained(rc);
-    if (!b->n_reads) return 0;
-    KitOnDevice* kd = nullptr;
-    if ((rc = kit_on_device(kit, c->device, &kd))) return drained(rc);
-    if ((rc = vote_buffer(c, 1))) return drained(rc);
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(c->vote_buf.get());
-    HIPCHK(hipMemsetAsync(d, 0, MAX_T * 8, c->stream));
-    HIPCHK(hipMemsetAsync(d + MAX_T, 0xFF, MAX_T * 8, c->stream));
-    const uint32_t blocks = std::min<uint32_t>((b->n_reads + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_vote, dim3(blocks), dim3(256), 0, c->stream, kd->kit, c->recs, b->n_reads, d, d + MAX_T);
-    HIPCHK(hipMemcpyAsync(hv, d, MAX_T * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(hf, d + MAX_T, MAX_T * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int qcat_detect_kit(qcat_ctx* c, const qcat_kit* ckit, const uint8_t* bases, const uint64_t* offsets,
-                               uint32_t n_reads, int64_t* votes, int64_t* first_read) {
-    if (!c || !ckit || !offsets || !votes || !first_read) return set_err(QCAT_ERR_ARG, "null argument");
-    qcat_kit* kit = const_cast<qcat_kit*>(ckit);
-    if (kit->hk.dk.ends != QCAT_ENDS_BOTH) return set_err(QCAT_ERR_ARG, "qcat_detect_kit needs a kit created with QCAT_ENDS_BOTH");
-    const int nt = kit->hk.dk.nt;
-    unsigned long long hv[MAX_T], hf[MAX_T];
-    qcat_batch* b = nullptr;
-    int rc = batch_upload_windows(c, kit, bases, offsets, n_reads, &b);
-    if (rc) return rc;
-    rc = vote_resident(c, kit, b, hv, hf);
-    qcat_batch_destroy(b);
-    if (rc) return rc;
-    for (int t = 0; t < nt; ++t) {
-        votes[t] += (int64_t)hv[t];
-        first_read[t] = hf[t] == ~0ull ? (int64_t)n_reads : (int64_t)hf[t];
-    }
-    return 0;
-}
-
-// the kit-auto scan of one batch.  Round 4: ONE host synchronisation -- the vote is counted AND decided on the device
-// (k_vote, k_pick_kit), the second pass reads the voted kit slot there (k_adapter_finish), and votes, choice, records and
-// counts come back together.  (Round 3 waited for the upload, for the votes and for the records: three round trips in a call
-// whose kernels take 0.3 ms.)
-static int scan_batch_auto_impl(qcat_ctx* c, const qcat_kit* ckit, const uint8_t* bases, const uint64_t* offsets,
-                                const uint8_t* const* ptrs, const uint64_t* lens,
-                                uint32_t n_reads, qcat_result* out, int64_t* counts, int32_t* chosen_kit_slot,
-                                int64_t* votes, int64_t* first_read, uint32_t batch_reads = 0) {
-    // batch_reads > 0 (round 4, the kit-auto file loop): the reads are consecutive batches of that many reads, each votes for
-    // a kit of its own (qcat/cli.py:500 calls detect_barcode_batch per batch) -- one adapter pass over all of them, the votes
-    // counted and decided per batch (k_vote / k_pick_kit with a batch dimension), the second pass takes every read's kit slot
-    // from its batch (k_adapter_finish: slot_span); chosen_kit_slot then has one entry per batch, votes / first_read are unused
-    if (!c || !ckit || (n_reads && !offsets && !ptrs) || !out || !chosen_kit_slot) return set_err(QCAT_ERR_ARG, "qcat_scan_batch_auto: null argument");
-    qcat_kit* kit = const_cast<qcat_kit*>(ckit);
-    const DevKit& hk = kit->hk.dk;
-    if (hk.ends != QCAT_ENDS_BOTH) return set_err(QCAT_ERR_ARG, "qcat_scan_batch_auto needs a kit created with QCAT_ENDS_BOTH");
-    const uint32_t nb = batch_reads ? (n_reads + batch_reads - 1) / batch_reads : 1u;
-    for (uint32_t q = 0; q < std::max(1u, nb); ++q) chosen_kit_slot[q] = -1;
-    if (!n_reads) return 0;                                     // (an empty batch: nobody votes, nothing to scan)
-    if (batch_reads && (votes || first_read)) return set_err(QCAT_ERR_ARG, "qcat_scan_batches_auto: the per-template votes are reported for one batch only");
-    qcat_batch* b = nullptr;
-    int rc = batch_upload_windows(c, kit, bases, offsets, n_reads, &b, ptrs, lens);
-    if (rc) return rc;
-    BatchPtr guard(b);
-    // (a failed step drains the stream before it returns: the upload may still be reading the pinned staging)
-    auto drained = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
-    KitOnDevice* kd = nullptr;
-    if ((rc = kit_on_device(kit, c->device, &kd))) return drained(rc);
-    if ((rc = vote_buffer(c, nb))) return drained(rc);
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(c->vote_buf.get());
-    unsigned long long* d_first = d + (size_t)nb * MAX_T;
-    int32_t* chosen_dev = reinterpret_cast<int32_t*>(d + 2 * (size_t)nb * MAX_T);
-    const uint32_t slot_span = batch_reads ? batch_reads * 2u : 0u;        // read ends per batch (both ends: checked above)
-    // the device work of the call, in stream order behind the upload
-    auto enqueue = [&]() -> int {
-        // pass 1: every template of every kit against both ends (qcat/scanner_base.py:662-678)
-        int e = scan_resident_impl(c, kit, b, ScanPass::vote());
-        if (e) return e;
-        {
-            FillScope fills(true);
-            HIPCHK(packed_fill(d, 0, (size_t)nb * MAX_T * 8, c->stream));
-            HIPCHK(packed_fill(d_first, 0xFF, (size_t)nb * MAX_T * 8, c->stream));
-            HIPCHK(packed_fill_flush(c->stream));
-        }
-        const uint32_t per = batch_reads ? batch_reads : n_reads;
-        const uint32_t blocks = std::min<uint32_t>((per + 255) / 256, batch_reads ? 64 : 1024);
-        hipLaunchKernelGGL(k_vote, dim3(blocks, nb), dim3(256), 0, c->stream, kd->kit, c->recs, n_reads, d, d_first, batch_reads);
-        hipLaunchKernelGGL(k_pick_kit, dim3(nb), dim3(64), 0, c->stream, kd->kit, d, d_first, chosen_dev);
-        // pass 2: detect_barcode per read with the voted kit's templates (:714-733): the adapter alignments of the vote are
-        // still on the device -- only their merge (the kit slot read from chosen_dev), the barcode phase and the finalisation run now
-        c->packed.kit_slot_dev = chosen_dev; c->packed.kit_slot_span = slot_span;
-        if (opt_on(QO_DEBUG_VOTE)) {                  // (diagnostics: the choice as the device made it, before the second pass)
-            unsigned long long dv[2 * MAX_T]; int32_t dc = -7;
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipMemcpy(dv, d, sizeof dv, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(&dc, chosen_dev, 4, hipMemcpyDeviceToHost);
-            fprintf(stderr, "[qcat] vote: chosen %d (kit slots %d, templates %d):", dc, hk.n_kit_slots, hk.nt);
-            for (int t = 0; t < hk.nt; ++t) fprintf(stderr, " %llu/slot%d", dv[t], hk.tpl[t].kit_slot);
-            fprintf(stderr, "\n");
-        }
-        return scan_resident_impl(c, kit, b, ScanPass::resume(RESUME_KIT_ON_DEVICE));
-    };
-    if ((rc = api_graph_run(c, c->api_graph, kit, kd, b, batch_reads, enqueue,
-                            [&] { c->packed.kit_slot_dev = chosen_dev; c->packed.kit_slot_span = slot_span; }))) return rc;
-    // what comes back, through the context's pinned block: the records, the vote buffer as it lies on the device (votes, first
-    // voting reads, chosen slots: one allocation), the counts -- three DMAs
-    const size_t bytes_rec = (size_t)n_reads * sizeof(qcat_result), bytes_vote = 2 * (size_t)nb * MAX_T * 8 + (size_t)nb * 4;
-    const size_t off_vote = (bytes_rec + 63) / 64 * 64, off_cnt = (off_vote + bytes_vote + 63) / 64 * 64;
-    const size_t need_ret = off_cnt + (size_t)hk.n_buckets * 8;
-    if (need_ret > c->pin_ret.cap()) {
-        (void)hipStreamSynchronize(c->stream);
-        HIPCHK(c->pin_ret.ensure(need_ret + need_ret / 4));
-    }
-    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(c->pin_ret, c->results, bytes_rec, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(c->pin_ret + off_vote, d, bytes_vote, hipMemcpyDeviceToHost, c->stream));
-    if (counts) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(c->pin_ret + off_cnt, c->counts, (size_t)hk.n_buckets * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(out, c->pin_ret, bytes_rec);
-    const unsigned long long* hv = reinterpret_cast<const unsigned long long*>(c->pin_ret + off_vote);
-    const unsigned long long* hf = hv + (size_t)nb * MAX_T;
-    const int32_t* chosen = reinterpret_cast<const int32_t*>(hf + (size_t)nb * MAX_T);
-    if (!batch_reads)
-        for (int t = 0; t < hk.nt; ++t) {
-            if (votes) votes[t] += (int64_t)hv[t];
-            if (first_read) first_read[t] = hf[t] == ~0ull ? (int64_t)n_reads : (int64_t)hf[t];
-        }
-    bool all_voted = true;
-    for (uint32_t q = 0; q < nb; ++q) { chosen_kit_slot[q] = chosen[q]; all_voted = all_voted && chosen[q] >= 0; }
-    if (!all_voted) return set_err(QCAT_ERR_DEVICE, "qcat_scan_batch_auto: no read voted");
-    if (counts) {
-        const int64_t* tmp = reinterpret_cast<const int64_t*>(c->pin_ret + off_cnt);
-        for (size_t i = 0; i < (size_t)hk.n_buckets; ++i) counts[i] += tmp[i];
-    }
-    return 0;
-}
-
-extern "C" int qcat_scan_batch_auto(qcat_ctx* c, const qcat_kit* ckit, const uint8_t* bases, const uint64_t* offsets,
-                                    uint32_t n_reads, qcat_result* out, int64_t* counts, int32_t* chosen_kit_slot,
-                                    int64_t* votes, int64_t* first_read) {
-    return scan_batch_auto_impl(c, ckit, bases, offsets, nullptr, nullptr, n_reads, out, counts, chosen_kit_slot, votes, first_read);
-}
-
-extern "C" int qcat_scan_batch_auto_ptrs(qcat_ctx* c, const qcat_kit* ckit, const uint8_t* const* reads, const uint64_t* lengths,
-                                         uint32_t n_reads, qcat_result* out, int64_t* counts, int32_t* chosen_kit_slot,
-                                         int64_t* votes, int64_t* first_read) {
-    if (n_reads && (!reads || !lengths)) return set_err(QCAT_ERR_ARG, "qcat_scan_batch_auto_ptrs: null argument");
-    return scan_batch_auto_impl(c, ckit, nullptr, nullptr, reads, lengths, n_reads, out, counts, chosen_kit_slot, votes, first_read);
-}
-
-extern "C" int qcat_scan_batches_auto_ptrs(qcat_ctx* c, const qcat_kit* ckit, const uint8_t* const* reads, const uint64_t* lengths,
-                                           uint32_t n_reads, uint32_t batch_reads, qcat_result* out, int64_t* counts, int32_t* chosen_kit_slots) {
-    if (n_reads && (!reads || !lengths)) return set_err(QCAT_ERR_ARG, "qcat_scan_batches_auto_ptrs: null argument");
-    if (!batch_reads) return set_err(QCAT_ERR_ARG, "qcat_scan_batches_auto_ptrs: batch_reads must be positive");
-    if (batch_reads >= n_reads)                                 // one batch: the plain call (small batches upload whole reads)
-        return scan_batch_auto_impl(c, ckit, nullptr, nullptr, reads, lengths, n_reads, out, counts, chosen_kit_slots, nullptr, nullptr);
-    if ((uint64_t)(n_reads + batch_reads - 1) / batch_reads > 65535u) return set_err(QCAT_ERR_ARG, "qcat_scan_batches_auto_ptrs: more than 65535 batches in one call");
-    return scan_batch_auto_impl(c, ckit, nullptr, nullptr, reads, lengths, n_reads, out, counts, chosen_kit_slots, nullptr, nullptr, batch_reads);
-}
-
-// ------------------------------------------------------------------------------------------
-// the driver's per-batch semantics on a resident batch: kit vote and --filter-barcodes without leaving the device
-// ------------------------------------------------------------------------------------------
-// what one such scan is: the batches of the vote and of the filter, and the chunks the adapter passes of a vote take them in
-struct ResidentBatchesJob {
-    uint32_t n, per, n_batches;         // per: reads of a batch (the whole resident batch when the caller gave 0 or more than it holds)
-    uint32_t chunk_batches;             // batches per adapter pass of a kit vote
-    bool kit_auto, filter;
-};
-
-static int resident_batches_check(const qcat_ctx* c, const qcat_kit* kit, const qcat_batch* b, uint32_t flags) {
-    if (!c || !kit || !b) return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: null argument");
-    if (flags & ~(uint32_t)(QCAT_RESIDENT_KIT_AUTO | QCAT_RESIDENT_FILTER_BARCODES))
-        return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: unknown flag");
-    if (b->device != c->device) return set_err(QCAT_ERR_ARG, "batch lives on another device than the context");
-    const DevKit& hk = kit->hk.dk;
-    if ((flags & QCAT_RESIDENT_KIT_AUTO) && hk.mode == QCAT_MODE_SIMPLE)
-        return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: simple mode has no kits to vote for (QCAT_RESIDENT_KIT_AUTO)");
-    if ((flags & QCAT_RESIDENT_KIT_AUTO) && hk.ends != QCAT_ENDS_BOTH)
-        return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: QCAT_RESIDENT_KIT_AUTO needs a kit created with QCAT_ENDS_BOTH");
-    return 0;
-}
-
-// the batches and the chunks; a scan this call could not finish is refused here, before anything is enqueued
-static int resident_batches_plan(const DevKit& hk, const qcat_batch* b, uint32_t batch_reads, uint32_t flags, ResidentBatchesJob& j) {
-    j.n = b->n_reads;
-    j.kit_auto = (flags & QCAT_RESIDENT_KIT_AUTO) != 0; j.filter = (flags & QCAT_RESIDENT_FILTER_BARCODES) != 0;
-    j.per = (batch_reads == 0 || batch_reads >= j.n) ? j.n : batch_reads;
-    j.n_batches = (j.n + j.per - 1) / j.per;
-    // one adapter pass over every template of every kit holds its alignments for the resumed pass: the file loop takes a
-    // million reads per call at most (fastq_host.inc), and so does this -- whole vote batches, 65535 of them at most (the
-    // grid of k_vote); a single batch larger than that is one pass, as it is for qcat_scan_resident
-    const uint64_t chunk_reads = (uint64_t)std::max<int64_t>(1, opt_val(QO_RESIDENT_AUTO_CHUNK, (int64_t)1 << 20));
-    j.chunk_batches = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(chunk_reads / j.per, 1), 65535);
-    if (!j.kit_auto || j.n_batches <= j.chunk_batches) j.chunk_batches = j.n_batches;
-    // the interior scan reads its batch from the first base on (absm_c2, the search of a base's read): it takes no view that
-    // starts inside a batch
-    if (j.kit_auto && hk.scan_middle && j.n_batches > j.chunk_batches)
-        return set_err(QCAT_ERR_UNSUPPORTED, "qcat_scan_resident_batches: a kit vote with scan_middle_adapter takes one adapter pass "
-                                             "(QCAT_HIP_RESIDENT_AUTO_CHUNK reads, 65535 batches) at most; scan the batch in parts");
-    return 0;
-}
-
-// one chunk of a kit vote: the vote pass over every template, the votes counted and decided per batch on the device, the
-// resumed pass with every read's kit slot from its batch -- scan_batch_auto_impl with a view of the resident batch where that
-// function's upload stands, the slots kept in c->kit_slots, the records from read r0 on in c->results
-static int resident_vote_chunk(qcat_ctx* c, qcat_kit* kit, KitOnDevice* kd, const qcat_batch* b, const ResidentBatchesJob& j, uint32_t q0, uint32_t qn) {
-    const uint32_t r0 = q0 * j.per, rn = (uint32_t)std::min<uint64_t>(j.n - r0, (uint64_t)qn * j.per);
-    const qcat_batch view = batch_view(b->device, rn, b->n_bases, b->bases, b->offsets + r0, nullptr);
-    const uint32_t span_reads = j.n_batches > 1 ? j.per : 0u;           // (0: one batch, one slot -- the form of qcat_scan_batch_auto)
-    int rc;
-    c->res_first = r0;
-    if ((rc = scan_resident_impl(c, kit, &view, ScanPass::vote().keeping_counts(q0 > 0)))) return rc;
-    if ((rc = vote_buffer(c, qn))) return rc;
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(c->vote_buf.get());
-    unsigned long long* d_first = d + (size_t)qn * MAX_T;
-    int32_t* chosen = c->kit_slots + q0;
-    {
-        FillScope fills(true);
-        HIPCHK(packed_fill(d, 0, (size_t)qn * MAX_T * 8, c->stream));
-        HIPCHK(packed_fill(d_first, 0xFF, (size_t)qn * MAX_T * 8, c->stream));
-        HIPCHK(packed_fill_flush(c->stream));
-    }
-    const uint32_t blocks = std::min<uint32_t>((j.per + 255) / 256, span_reads ? 64 : 1024);
-    hipLaunchKernelGGL(k_vote, dim3(blocks, qn), dim3(256), 0, c->stream, kd->kit, c->recs, rn, d, d_first, span_reads);
-    hipLaunchKernelGGL(k_pick_kit, dim3(qn), dim3(64), 0, c->stream, kd->kit, d, d_first, chosen);
-    c->packed.kit_slot_dev = chosen; c->packed.kit_slot_span = span_reads * 2u;
-    return scan_resident_impl(c, kit, &view, ScanPass::resume(RESUME_KIT_ON_DEVICE).keeping_counts(q0 > 0).deferring_counts(j.filter));
-}
-
-extern "C" int qcat_scan_resident_batches(qcat_ctx* c, const qcat_kit* ckit, const qcat_batch* b, uint32_t batch_reads, uint32_t flags) {
-    int rc = resident_batches_check(c, ckit, b, flags);
-    if (rc) return rc;
-    if (!flags) return qcat_scan_resident(c, ckit, b);                  // the same launches, the same records
-    qcat_kit* kit = const_cast<qcat_kit*>(ckit);
-    const DevKit& hk = kit->hk.dk;
-    if (!b->n_reads) {                                                  // nobody votes, nothing to filter: zero batches
-        if ((rc = scan_resident_impl(c, kit, b, ScanPass::plain()))) return rc;
-        if (flags & QCAT_RESIDENT_KIT_AUTO) c->auto_batches = 0;
-        return 0;
-    }
-    if (b->true_len) return set_err(QCAT_ERR_ARG, "qcat_scan_resident_batches: the batch holds read windows, not whole reads");
-    ResidentBatchesJob j{};
-    if ((rc = resident_batches_plan(hk, b, batch_reads, flags, j))) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    KitOnDevice* kd = nullptr;
-    if ((rc = kit_on_device(kit, c->device, &kd))) return rc;
-    // a failure below leaves no scan behind: no records to fetch or to partition, no slots
-    auto failed = [&](int code) { c->res_first = 0; c->last_kit = nullptr; c->last_n_reads = 0; c->auto_batches = -1; return code; };
-    if (j.kit_auto) {
-        // the records of every chunk in read order in c->results: sized for the whole batch first, so that no chunk's scan moves it
-        if ((rc = grow(c->results, (size_t)j.n))) return failed(rc);
-        if ((rc = grow(c->kit_slots, (size_t)j.n_batches))) return failed(rc);
-        for (uint32_t q0 = 0; q0 < j.n_batches; q0 += j.chunk_batches)
-            if ((rc = resident_vote_chunk(c, kit, kd, b, j, q0, std::min(j.chunk_batches, j.n_batches - q0)))) return failed(rc);
-        c->res_first = 0;
-    } else if ((rc = scan_resident_impl(c, kit, b, ScanPass::plain().deferring_counts(true)))) return failed(rc);
-    if (j.filter) {
-        // behind k_finalize and the interior scan, in front of the counts: the counts are those of the filtered records
-        const KitPtrs kp{kd->kit, kd->codes, kd->ids, kd->tables};
-        if ((rc = filter_run(c, hk, kp, c->results, j.n, j.per))) return failed(rc);
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>((j.n + 255) / 256, hk.n_buckets > 2048 ? 512 : 1024);
-        hipLaunchKernelGGL(k_count, dim3(blocks), dim3(256), 0, c->stream, kp, (const qcat_result*)c->results.get(), (const uint64_t*)b->offsets,
-                           (const uint32_t*)nullptr, j.n, c->counts.get());
-        mark(c, "k_count");
-        if (hipGetLastError() != hipSuccess) return failed(set_err(QCAT_ERR_DEVICE, "qcat_scan_resident_batches: launch of k_count failed"));
-    }
-    c->last_kit = kit; c->last_n_reads = j.n; c->last_buckets = hk.n_buckets;
-    c->auto_batches = j.kit_auto ? (int64_t)j.n_batches : -1;
-    return 0;
-}
-
-extern "C" int qcat_ctx_fetch_kit_slots(qcat_ctx* c, int32_t* slots, uint32_t n_batches) {
-    if (!c || (!slots && n_batches)) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_kit_slots: null argument");
-    if (c->auto_batches < 0)
-        return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_kit_slots: this context's latest scan was no qcat_scan_resident_batches with QCAT_RESIDENT_KIT_AUTO");
-    if ((int64_t)n_batches != c->auto_batches) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_kit_slots: n_batches does not match the latest scan");
-    HIPCHK(hipSetDevice(c->device));
-    if (n_batches) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(slots, c->kit_slots, (size_t)n_batches * 4, hipMemcpyDeviceToHost, c->stream));
-    return stream_done(c, "qcat_ctx_fetch_kit_slots");
 }
 
 extern "C" int qcat_scan_batch(qcat_ctx* c, const qcat_kit* kit,

@@ -278,3 +278,75 @@ def test_adapter_chains_of_a_small_batch_in_one_launch(kit, n, hip_options):
         cnt2 = np.zeros(desc.n_count_buckets, dtype=np.int64)             # (and without the traces: the records-only kernels)
         assert native.NativeContext(0).scan(native.NativeKit(desc), bases, offsets, counts=cnt2).tobytes() == o_recs.tobytes(), variant
         assert np.array_equal(cnt2, o_cnt), variant
+
+
+def _host_choice(kit, votes, first, n):
+    """the kit slot the reference's fold picks from per-template votes (BarcodeScanner.detect_kit): most votes, then the kit
+    that voted first"""
+    counts, seen = {}, {}
+    for t, lay in enumerate(kit.descriptor.layouts):
+        if votes[t]:
+            s = kit.descriptor.kit_slots[lay.kit]
+            counts[s] = counts.get(s, 0) + int(votes[t])
+            seen[s] = min(seen.get(s, n), int(first[t]))
+    return sorted(counts, key=lambda s: (-counts[s], seen[s]))[0] if counts else -1
+
+
+def test_vote_routes_agree(hip_options):
+    """The kit vote has four routes to one device sequence (fill, k_vote, k_pick_kit): qcat_detect_kit + the host's fold,
+    qcat_scan_batch_auto, qcat_scan_batches_auto_ptrs and qcat_scan_resident_batches (here in two vote chunks).  1203 reads
+    of three majorities, batches of 400 and a last one of 3: the same slot per batch on every route, the same votes and
+    first voters where a route reports them, byte-identical records where a route returns records -- and the same again
+    from a second pass over the same calls, in which the captured graph replays."""
+    det = scanner.factory()
+    cfg = config.qcatConfig()
+    lib = native.HipLibrary.get().lib
+    ctx = native.NativeContext(0)
+    kit = det._native_kit(det.layouts, cfg, native.ENDS_BOTH)
+    nt, per = len(kit.descriptor.layouts), 400
+    reads = []
+    for m, s in (("PBC096", 41), ("RBK004", 42), ("NBD104/NBD114", 43)):
+        reads += _mixed_batch(det, m, 400, s)[:400]
+    reads += _mixed_batch(det, "PBC096", 400, 44)[:3]
+    assert len(reads) == 1203
+    bases, offsets = native.pack_reads(reads)
+    parts = [native.pack_reads(reads[r0:r0 + per]) for r0 in range(0, len(reads), per)]
+    # one pointer and one length per read over the packed bases: the form of native.read_views, without the C helper
+    views = ((bases.ctypes.data + offsets[:-1]).astype(np.uint64).tobytes(), np.diff(offsets).astype(np.uint64).tobytes())
+    batch = native.ResidentBatch.upload(ctx, bases, offsets)
+    hip_options(RESIDENT_AUTO_CHUNK=800)
+
+    def routes():
+        a_votes, a_slots, b_votes, b_slots, b_recs = [], [], [], [], []
+        for pb, po in parts:
+            n = len(po) - 1
+            votes, first = ctx.detect_kit(kit, pb, po)
+            a_votes.append((votes.tolist(), first.tolist()))
+            a_slots.append(_host_choice(kit, votes, first, n))
+            out = np.zeros(n, dtype=native.RESULT_DTYPE)
+            v, f = np.zeros(nt, dtype=np.int64), np.zeros(nt, dtype=np.int64)
+            slot = native.C.c_int32(-1)
+            ctx.hip.check(lib.qcat_scan_batch_auto(ctx.handle, kit.handle, pb.ctypes.data, po.ctypes.data, n, out.ctypes.data, None,
+                                                   native.C.byref(slot), v.ctypes.data, f.ctypes.data))
+            b_votes.append((v.tolist(), f.tolist())); b_slots.append(int(slot.value)); b_recs.append(out)
+        c = [ctx.scan_batches_auto_views(kit, views, len(reads), per) for _ in range(3)]     # plain, capture, replay
+        d_recs, _counts, d_slots = ctx.scan_resident_batches(kit, batch, per, kit_auto=True)
+        return a_votes, a_slots, b_votes, b_slots, np.concatenate(b_recs), c, d_recs, d_slots.tolist()
+
+    first_pass = None
+    for _ in range(2):
+        before = lib.qcat_ctx_graph_replays(ctx.handle)
+        a_votes, a_slots, b_votes, b_slots, b_recs, c, d_recs, d_slots = routes()
+        assert lib.qcat_ctx_graph_replays(ctx.handle) > before
+        assert len(a_slots) == 4 and len(set(a_slots[:3])) == 3 and min(a_slots) >= 0
+        assert [kit.descriptor.kit_names[s] for s in a_slots[:3]] == ["PBC096", "RBK004", "NBD104/NBD114"]
+        assert a_slots == b_slots == d_slots
+        assert a_votes == b_votes
+        assert [sum(v) for v, _f in a_votes] == [400, 400, 400, 3]
+        for c_recs, c_slots in c:
+            assert c_slots.tolist() == a_slots
+            assert c_recs.tobytes() == b_recs.tobytes()
+        assert d_recs.tobytes() == b_recs.tobytes()
+        if first_pass is None:
+            first_pass = (a_votes, a_slots, b_recs.tobytes())
+        assert first_pass == (a_votes, a_slots, b_recs.tobytes())

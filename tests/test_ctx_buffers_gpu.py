@@ -167,7 +167,7 @@ def test_a_reallocation_drops_a_captured_graph():
 def test_pipeline_stages_grow_between_calls(hip_options):
     """chunks of 4096 reads: a 33 000-read call sizes the two stage slots, a 70 000-read call on the same context reuses them (a
     slot is sized by the largest chunk, not by the batch); the same 70 000 reads in chunks of 8192 then grow the slots by the
-    capped factor (host_pipeline.inc), and chunks of 4096 run once more in the slots that are now too big -- every call against
+    capped factor (pipeline_core.h: stage_need), and chunks of 4096 run once more in the slots that are now too big -- every call against
     the oracle.  The batches repeat the 6000 PBC096 reads of the first test (ragged reads among them, which land at other
     places of a chunk in every repetition)."""
     d, uniq, o_recs, o_cnt, _ = _families()["bitslice6000"]

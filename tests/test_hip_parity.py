@@ -283,7 +283,7 @@ def test_host_buffer_scan_uploads_windows_only():
                                                 (None, "dual", native.ENDS_BOTH)])
 def test_host_buffer_scan_pipeline_equals_one_shot_and_oracle(kit_name, mode, ends, monkeypatch):
     """qcat_scan_batch on >= 32 768 reads runs as a chunked pipeline (host compaction | H2D | kernels,
-    host_pipeline.inc): records and counts must equal the one-shot path's and the oracle's, for chunk
+    pipeline_host.inc): records and counts must equal the one-shot path's and the oracle's, for chunk
     sizes that do and do not divide the batch, with ragged reads at chunk borders, and repeated calls
     on one context must reuse its staging without leaking state."""
     det = scanner.factory(mode=mode, kit=kit_name)
