@@ -478,6 +478,50 @@ int  qcat_batch_from_device(qcat_ctx* ctx, const void* d_bases, const void* d_qu
  * allocation each.  A batch that is not whole reads of its own (what the partition refuses): QCAT_ERR_ARG. */
 int  qcat_batch_devptrs(const qcat_batch* batch, const void** bases, const void** qualities, const void** offsets);
 
+/* ---- FASTQ text in HBM: a text goes up, the bytes of every per-barcode .fastq file come down ----
+ * replaces, for reads that stay in HBM: the reader of the reference driver (qcat/cli.py:235-306, FastqGeneralIterator and
+ * extract_fastx_comment) in front of the scan and its per-barcode FASTQ writer (qcat/cli.py:327-342 behind :514-530) behind it.
+ * The host splits no record and formats none: a plain four-line record already holds title, bases and qualities, so the uploaded
+ * text is the title and quality store, and a record of an output file is a few byte ranges of it plus three constant strings. */
+/* text: host pointer to the n_bytes bytes of a FASTQ file or segment.  out = an OWNED resident batch with the bases (compact,
+ * the usual slack) and offsets[n + 1] that qcat_batch_upload of the host-parsed reads would hold, no quality plane, and besides
+ * a text plane -- the uploaded bytes, tabs inside titles turned into blanks ("the titles as the writers print them",
+ * header.replace("\t", " ")), a block of constants behind them -- and a record table in device memory: per read title_off,
+ * title_len, seq_off, seq_len, qual_off with the meanings of qcat_fastq_read_info (the title without '@', right-stripped of
+ * blanks and tabs).  Every batch function works on it as on any owned batch.
+ * Accepted is exactly what qcat_fastq_open accepts of a FASTQ file: '@' title lines without control characters but tab and
+ * without bytes >= 0x80, one non-empty sequence line of bytes 0x21..0x7F, a '+' line alone, followed by blanks or by the same
+ * title, a quality line of the same length and class, a last record that may lack its newline, nothing behind it.  Anything
+ * else, and FASTA text (first byte '>'): QCAT_ERR_UNSUPPORTED with "... (record N)", N the 1-based number of the first record
+ * that is not plain; no batch is left behind, the context stays usable.  An empty text: a batch of 0 reads.
+ * Record count, line starts and every check are computed on the device; the host waits twice for eight bytes (the number of
+ * lines, which sizes the tables; the verdict with the number of bases) and once for the bases' copy. */
+int  qcat_batch_upload_fastq_text(qcat_ctx* ctx, const uint8_t* text, uint64_t n_bytes, qcat_batch** out);
+/* the record table of a text batch, n_reads entries each (any array may be NULL): the counterpart of qcat_fastq_read_info.
+ * A batch without a text plane: QCAT_ERR_ARG. */
+int  qcat_batch_fetch_text_records(qcat_ctx* ctx, const qcat_batch* batch, uint64_t* title_off, uint32_t* title_len,
+                                   uint64_t* seq_off, uint32_t* seq_len);
+/* The per-barcode FASTQ text of a text batch by the calls of `records` (as in qcat_batch_partition: NULL = this context's
+ * latest qcat_scan_resident / qcat_scan_resident_batches of these reads with `kit`): ONE device buffer, owned by ctx until its
+ * next call of this function, with the records in (bin, index in the batch) order -- the bins of qcat_kit_partition_bins, the
+ * order of qcat_batch_partition, whose keys, slices and sort these are.  A record's bytes are
+ *   '@' title' '\n' seq[a:b] "\n+\n" qual[a:b] '\n'
+ * with [a:b) the partition's kept slice and title' the stored title plus one blank when it holds none (qcat/cli.py:338 prints
+ * name + " " + comment; an empty title prints "@ ").  A read the minimum-length filter drops contributes 0 bytes -- the driver
+ * writes nothing for it --, so the last bin is empty.  *n_text_bytes = the size of the text.
+ * flags: reserved, must be 0.  A batch without a text plane: QCAT_ERR_ARG; 6 * n_reads >= 2^32: QCAT_ERR_UNSUPPORTED before
+ * anything is enqueued.  Takes the scratch of qcat_batch_partition (the context's latest partition is gone afterwards).
+ * Enqueues on the context's stream, synchronises once (the total).  The result is the same bytes run after run. */
+int  qcat_batch_demux_text(qcat_ctx* ctx, const qcat_kit* kit, const qcat_batch* batch, const qcat_result* records,
+                           uint32_t flags, uint64_t* n_text_bytes);
+/* the latest text of this context: text (cap >= its size), bin_first_bytes[n_bins + 1] (bin b = bytes [bin_first_bytes[b],
+ * bin_first_bytes[b+1])), rec_first[n_reads + 1] (the first byte of every record in sorted order) and source[n_reads] (index in
+ * the batch of the sorted order's reads).  Any of the four may be NULL. */
+int  qcat_ctx_fetch_demux_text(qcat_ctx* ctx, uint8_t* text, uint64_t cap, uint64_t* bin_first_bytes, int32_t n_bins,
+                               uint64_t* rec_first, uint32_t* source);
+/* the text in device memory (owned by ctx until its next qcat_batch_demux_text), for callers that stay in HBM */
+void* qcat_ctx_demux_text_devptr(qcat_ctx* ctx);
+
 /* the latest partition of this context: bin b = reads [bin_first[b], bin_first[b+1]) of `out`
  * (n_bins + 1 entries); source[i] = index in the input batch of read i of `out` (n_reads entries, may be NULL) */
 int  qcat_ctx_fetch_partition(qcat_ctx* ctx, uint64_t* bin_first, int32_t n_bins, uint32_t* source);

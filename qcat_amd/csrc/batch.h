@@ -8,6 +8,7 @@
 #include "../../include/qcat_hip.h"
 #include "dev_buf.h"
 #include "partition_core.h"
+#include "fqtext_core.h"
 
 constexpr size_t BATCH_SLACK = 64;                 // bytes in front of and behind a batch's bases
 static_assert(BATCH_SLACK == qpart::PART_SLACK, "the partition's copy kernel relies on the batches' slack");
@@ -22,12 +23,20 @@ struct qcat_batch {
                                    // laid out like the bases'; no scan reads it, the partition moves it with the bases
     uint64_t* offsets = nullptr;   // n_reads + 1
     uint32_t* true_len = nullptr;  // window-only batches (batch_upload_windows): the reads' real lengths
+    // a batch parsed from FASTQ text on the device (qcat_batch_upload_fastq_text, fqtext_host.inc; null: none): the text plane --
+    // BATCH_SLACK bytes into an allocation of BATCH_SLACK + text_bytes + qfq::FQ_CONST_BYTES + BATCH_SLACK bytes, the titles as the
+    // writers print them (tabs are blanks), the constants block behind the text -- and the record table, one entry per read
+    uint8_t* text = nullptr;
+    uint64_t text_bytes = 0;
+    qfq::Rec* text_recs = nullptr;
 
     // the planes of a batch that owns its memory (fixed size, the caller's: no generation bump); a view -- the device buffers
     // belong to a context (host-buffer calls) or a pipeline stage -- leaves them empty, and destroying it frees the shell only
     struct Store {
         qk::FixedBuf<uint8_t> bases, quals;
         qk::FixedBuf<uint64_t> offsets;
+        qk::FixedBuf<uint8_t> text;
+        qk::FixedBuf<qfq::Rec> text_recs;
     } store;
     bool owned() const { return store.bases.get() != nullptr; }
 
@@ -73,9 +82,23 @@ struct FilterScratch {
     qk::DevBuf<uint32_t> table, floor;
     qk::DevBuf<qcat_result> recs;
 };
+// FASTQ text on the device (kernels_fqtext.inc, fqtext_host.inc): the parse's block counts, line table, status and copy tables;
+// the segment table, the arrays and the text of the latest qcat_batch_demux_text (`source`: a copy of the partition scratch's
+// sorted order, which the next partition overwrites)
+struct FqTextScratch {
+    qk::DevBuf<uint64_t> counts, sums, line_start, seq_src, status;
+    qk::DevBuf<uint32_t> chunk_first;
+    qk::DevBuf<uint64_t> seg_off, seg_src, rec_first, bin_bytes;
+    qk::DevBuf<uint8_t> out;                   // BATCH_SLACK in front of the text, like a batch's planes
+    qk::DevBuf<uint32_t> source;
+    uint32_t n_reads = 0;
+    int32_t n_bins = 0;                        // 0: no demultiplexed text yet
+    uint64_t total = 0;
+};
 // what a context keeps for the batch functions
 struct BatchScratch {
     PartScratch part;
     FilterScratch filter;
+    FqTextScratch fqtext;
     qk::DevBuf<uint32_t> offs_bad;             // qcat_batch_from_device: the flag of k_offsets_check
 };

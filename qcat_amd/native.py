@@ -402,6 +402,11 @@ class HipLibrary(object):
             "qcat_ctx_results_devptr": (vp, [vp]),
             "qcat_batch_partition": (C.c_int, [vp, vp, vp, vp, u32, C.POINTER(vp)]),
             "qcat_ctx_fetch_partition": (C.c_int, [vp, vp, i32, vp]),
+            "qcat_batch_upload_fastq_text": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(vp)]),
+            "qcat_batch_fetch_text_records": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+            "qcat_batch_demux_text": (C.c_int, [vp, vp, vp, vp, u32, C.POINTER(C.c_uint64)]),
+            "qcat_ctx_fetch_demux_text": (C.c_int, [vp, vp, C.c_uint64, vp, i32, vp, vp]),
+            "qcat_ctx_demux_text_devptr": (vp, [vp]),
             "qcat_ctx_partition_bins_devptr": (vp, [vp]),
             "qcat_ctx_partition_source_devptr": (vp, [vp]),
             "qcat_ctx_last_timing": (C.c_int, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
@@ -648,6 +653,33 @@ class ResidentBatch(object):
                                                  int(n_reads), C.byref(h)))
         return cls(ctx, h)
 
+    class Unsupported(RuntimeError):
+        """the text is not plain four-line FASTQ (the message names the first record that is not)"""
+
+    @classmethod
+    def upload_fastq_text(cls, ctx, text):
+        """qcat_batch_upload_fastq_text: the bytes of a FASTQ file, parsed on the device into a batch with bases, offsets, a text
+        plane and a record table (:meth:`text_records`); :class:`ResidentBatch.Unsupported` when the text is not plain"""
+        hip = HipLibrary.get()
+        if isinstance(text, str):
+            text = text.encode("latin-1")
+        buf = np.frombuffer(text, dtype=np.uint8)
+        h = C.c_void_p()
+        rc = hip.lib.qcat_batch_upload_fastq_text(ctx.handle, buf.ctypes.data if len(buf) else None, len(buf), C.byref(h))
+        if rc == -2:
+            raise cls.Unsupported("qcat_hip error -2: " + (hip.lib.qcat_last_error() or b"").decode("utf-8", "replace"))
+        hip.check(rc)
+        return cls(ctx, h)
+
+    def text_records(self):
+        """qcat_batch_fetch_text_records: (title_off uint64, title_len uint32, seq_off uint64, seq_len uint32), one entry per read"""
+        n = self.n_reads
+        to, tl = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+        so, sl = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+        self.hip.check(self.hip.lib.qcat_batch_fetch_text_records(self.ctx.handle, self.handle, to.ctypes.data, tl.ctypes.data,
+                                                                  so.ctypes.data, sl.ctypes.data))
+        return to, tl, so, sl
+
     @property
     def has_qualities(self):
         rc = self.hip.lib.qcat_batch_has_qualities(self.handle)
@@ -746,6 +778,15 @@ class Partition(object):
         return [raw[offsets[i]:offsets[i + 1]] for i in range(int(self.bin_first[b]), int(self.bin_first[b + 1]))]
 
 
+class DemuxText(object):
+    """What :meth:`NativeContext.demux_text` returns: ``text`` (a memoryview of bytes, sliced without a copy: the records of
+    every bin in (bin, index in the batch) order), ``bin_first_bytes`` (uint64, bins + 1 entries), ``rec_first`` (uint64, reads + 1: the first byte of every record in
+    sorted order) and ``source`` (uint32: index in the batch of the sorted order's reads)."""
+
+    def __init__(self, text, bin_first_bytes, rec_first, source):
+        self.text, self.bin_first_bytes, self.rec_first, self.source = text, bin_first_bytes, rec_first, source
+
+
 class NativeContext(object):
     """``qcat_ctx*`` handle: one device, one stream; not re-entrant."""
 
@@ -841,6 +882,30 @@ class NativeContext(object):
         source = np.zeros(part.n_reads, dtype=np.uint32)
         self.hip.check(self.hip.lib.qcat_ctx_fetch_partition(self.handle, bin_first.ctypes.data, n_bins, source.ctypes.data))
         return Partition(part, bin_first, source)
+
+    def demux_text(self, kit, batch, records=None):
+        """qcat_batch_demux_text of a batch made by :meth:`ResidentBatch.upload_fastq_text`: the bytes of the per-barcode FASTQ
+        files, formatted on the device -- a :class:`DemuxText`.  ``records`` as in :meth:`partition`."""
+        handle = kit.handle
+        last = getattr(self, "_resident_scan", None)
+        if records is None and last is not None and last[0] is kit:
+            handle = last[1]
+        if records is not None:
+            records = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
+            if len(records) != batch.n_reads:
+                raise RuntimeError("demux_text: {} records for a batch of {} reads".format(len(records), batch.n_reads))
+        total = C.c_uint64()
+        self.hip.check(self.hip.lib.qcat_batch_demux_text(self.handle, handle, batch.handle,
+                                                          records.ctypes.data if records is not None else None, 0, C.byref(total)))
+        n, n_bins = batch.n_reads, self.hip.lib.qcat_kit_partition_bins(handle)
+        text = np.empty(int(total.value), dtype=np.uint8)
+        bin_first_bytes = np.zeros(n_bins + 1, dtype=np.uint64)
+        rec_first = np.zeros(n + 1, dtype=np.uint64)
+        source = np.zeros(n, dtype=np.uint32)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_demux_text(self.handle, text.ctypes.data if len(text) else None, len(text),
+                                                              bin_first_bytes.ctypes.data, n_bins, rec_first.ctypes.data,
+                                                              source.ctypes.data if n else None))
+        return DemuxText(memoryview(text), bin_first_bytes, rec_first, source)
 
     def detect_kit(self, kit, bases, offsets):
         """per-template (votes, first voting read) of qcat_detect_kit."""

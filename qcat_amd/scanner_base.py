@@ -469,16 +469,75 @@ class BarcodeScanner(object):
         kits votes a kit per batch on the device (``qcat/scanner_base.py:662-678``); a scanner made with
         ``enable_filter_barcodes`` filters every batch there (``:690-712``); ``scan_middle_adapter`` is part of the kit.
         Returns what :meth:`demux_batch` returns; under a kit vote the bins are the Barcode ids of all kits, one bin per id."""
+        kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
+        return self._demux_resident(kit, read_sequences, read_qualities, scan)
+
+    def _batches_scan(self, batch_size, trim, min_read_length, qcat_config):
+        """the kit and the resident scan of :meth:`demux_batches` and :meth:`demux_fastq_text`: ``scan(ctx, batch)`` with the
+        driver's per-batch semantics -- the vote of a scanner with several kits, the barcode filter"""
         if qcat_config is None:
             qcat_config = config.qcatConfig()
         if not self.layouts and self._native_mode != "simple":
             raise IndexError("list index out of range")
         kit_auto = self._native_mode != "simple" and len(set(l.kit for l in self.layouts)) > 1
         kit = self._native_kit(self.layouts, qcat_config, native.ENDS_BOTH, min_read_length=min_read_length, trim=trim)
-        return self._demux_resident(kit, read_sequences, read_qualities,
-                                    lambda ctx, batch: ctx.scan_resident_batches(kit, batch, int(batch_size), kit_auto=kit_auto,
-                                                                                 filter_barcodes=bool(self.enable_filter_barcodes),
-                                                                                 fetch=False))
+        return kit, (lambda ctx, batch: ctx.scan_resident_batches(kit, batch, int(batch_size), kit_auto=kit_auto,
+                                                                  filter_barcodes=bool(self.enable_filter_barcodes), fetch=False))
+
+    def demux_fastq_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None):
+        """:meth:`demux_batches` from FASTQ text to FASTQ text: the bytes of a plain four-line FASTQ file go up, are parsed on the
+        device (qcat_batch_upload_fastq_text), scanned like :meth:`demux_batches` scans, and the bytes of every per-barcode
+        ``.fastq`` file come down as the reference driver writes them (``qcat/cli.py:327-342`` behind ``:514-530``), formatted on
+        the device (qcat_batch_demux_text).  Returns ``{file name: bytes}`` with the names of ``get_output_file``
+        (``qcat/cli.py:309-324``): ``Barcode.name`` with ``/`` replaced by ``_`` plus ``.fastq``, ``none.fastq`` for reads without
+        a call, nothing for reads the minimum-length filter drops.  Kits name the same id differently, so one bin is not always
+        one file: the name of every record comes from its record (under a vote: of the kit its batch voted for); a bin with
+        one name is sliced out whole, a bin with several record by record, in file order either way.  No record is formatted
+        here.  Text that is not plain: :class:`native.ResidentBatch.Unsupported`."""
+        kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
+        ctx = self._context()
+        batch = native.ResidentBatch.upload_fastq_text(ctx, text)
+        try:
+            n = batch.n_reads
+            scan(ctx, batch)
+            out = ctx.demux_text(kit, batch)
+            recs = np.zeros(n, dtype=native.RESULT_DTYPE)
+            ctx.hip.check(ctx.hip.lib.qcat_ctx_fetch_results(ctx.handle, recs.ctypes.data, n))
+        finally:
+            batch.destroy()
+        rec_first = out.rec_first.astype(np.int64)
+        bin_bytes = out.bin_first_bytes.astype(np.int64)
+        kept = int(np.count_nonzero(np.diff(rec_first)))                         # (skipped reads: the last bin, 0 bytes each)
+        src = out.source[:kept]
+        calls = recs[src]
+        key = ((calls["adapter_idx"].astype(np.int64) + 1) << 42) | ((calls["barcode_idx"].astype(np.int64) + 1) << 21) \
+            | (calls["barcode2_idx"].astype(np.int64) + 1)
+        _u, first, call_of = np.unique(key, return_index=True, return_inverse=True)
+        # the distinct file names, and the name of every distinct call: the templates of one kit share their barcodes' names
+        names, name_index = [], []
+        for d in self._records_to_dicts(calls[first], self.layouts):
+            bc_id = "none"
+            if d["barcode"]:
+                bc_id = d["barcode"].name
+                if bc_id:
+                    bc_id = bc_id.replace("/", "_")
+            name = "{}.fastq".format(bc_id)
+            if name not in names:
+                names.append(name)
+            name_index.append(names.index(name))
+        name_of = np.asarray(name_index, dtype=np.int64)[call_of.reshape(-1)] if kept else np.zeros(0, dtype=np.int64)
+        files = {}
+        bin_rec = np.searchsorted(rec_first[:kept + 1], bin_bytes)               # the first sorted record of every bin
+        for b in np.flatnonzero(np.diff(bin_bytes) > 0).tolist():
+            j0, j1 = int(bin_rec[b]), int(bin_rec[b + 1])
+            ids = name_of[j0:j1]
+            if ids.min() == ids.max():
+                files.setdefault(names[int(ids[0])], []).append(out.text[bin_bytes[b]:bin_bytes[b + 1]])
+                continue
+            for u in ids[np.sort(np.unique(ids, return_index=True)[1])].tolist():   # the bin's names in order of appearance
+                files.setdefault(names[u], []).append(b"".join(out.text[rec_first[j]:rec_first[j + 1]]
+                                                               for j in (np.flatnonzero(ids == u) + j0).tolist()))
+        return {name: b"".join(parts) for name, parts in files.items()}
 
     def _demux_resident(self, kit, read_sequences, read_qualities, scan):
         """upload, ``scan(ctx, batch)``, partition, and the bins as :meth:`demux_batch` returns them"""
