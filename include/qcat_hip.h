@@ -522,6 +522,42 @@ int  qcat_ctx_fetch_demux_text(qcat_ctx* ctx, uint8_t* text, uint64_t cap, uint6
 /* the text in device memory (owned by ctx until its next qcat_batch_demux_text), for callers that stay in HBM */
 void* qcat_ctx_demux_text_devptr(qcat_ctx* ctx);
 
+/* ---- the driver's TSV table of a text batch, formatted in device memory ----
+ * What the rows print besides the bytes of the text: per template of the kit (the meanings of qcat_demux_opts). */
+typedef struct qcat_tsv_names {
+    const char* const* kit_name;         /* AdapterLayout.kit; NULL entry prints "None" (simple mode) */
+    const int32_t* const* bc_id;         /* Barcode.id of sets[0] */
+    const int32_t* const* bc2_id;        /* dual mode: ids of sets[1]; NULL otherwise */
+} qcat_tsv_names;
+/* The rows of `--tsv` for a text batch by the calls of `records` (as in qcat_batch_demux_text: NULL = this context's latest
+ * qcat_scan_resident / qcat_scan_resident_batches of these reads with `kit`): ONE device buffer, owned by ctx until its next call
+ * of this function, with one row per kept read in read order and no header line -- byte for byte what qcat_fastq_demux writes to
+ * tsv_fd for the same file, kit and options:
+ *   name \t kept length \t id \t score \t kit \t adapter_end \t comment \n      a called read (dual mode: id "/" id2)
+ *   name \t kept length \t none \t -1 \t none \t -1 \t comment \n               any other read
+ * name = the stored title up to its first blank, comment = the bytes behind it ("None" when the title holds no blank; the text
+ * plane holds tabs as blanks).  Kept length and dropped reads are the partition's (the kept slice of qcat_batch_partition, the
+ * kit's min_read_length): a dropped read has a row of 0 bytes.  A read is called exactly when the host writer calls it: the
+ * simple-mode rule of qcat_fastq_demux, and an index outside the kit's templates or the name tables counts as "not called".
+ * id = str(Barcode.id), kit = kit_name[adapter_idx] ("None" in simple mode), score = Python's repr(raw_score * 100.0 /
+ * (1.0 * score_den)), looked up in a table the host builds once per kit: every denominator the kit can write to score_den
+ * (every set's target length, the barcodes' own lengths of a ragged simple list) with the raw scores 0 .. den * (the largest
+ * entry of barcode_matrix), 24 bytes per entry.  A kit whose table would exceed 1 MiB (43 690 entries), a score text of more
+ * than 23 characters or a kit name of more than 63 bytes: QCAT_ERR_UNSUPPORTED before anything is enqueued.
+ * flags: reserved, must be 0.  QCAT_ERR_ARG, the context stays usable: a batch without a text plane, NULL `names` or a NULL table
+ * in it, records == NULL without a matching scan, and a called record whose (raw_score, score_den) lies outside the score table
+ * (a flag the device raises, read at the call's one synchronisation; no text is left behind).
+ * Uses scratch of its own, not the partition's: a context keeps its latest demultiplexed text and its latest TSV text side by
+ * side.  Enqueues on the context's stream, synchronises once (the total).  The result is the same bytes run after run.
+ * *n_text_bytes = the size of the text. */
+int  qcat_batch_tsv_text(qcat_ctx* ctx, const qcat_kit* kit, const qcat_batch* batch, const qcat_result* records,
+                         const qcat_tsv_names* names, uint32_t flags, uint64_t* n_text_bytes);
+/* the latest TSV text of this context: text (cap >= its size) and row_first[n_reads + 1] (row r = bytes [row_first[r],
+ * row_first[r+1]), empty for a dropped read).  Either may be NULL. */
+int  qcat_ctx_fetch_tsv_text(qcat_ctx* ctx, uint8_t* text, uint64_t cap, uint64_t* row_first);
+/* the text in device memory (owned by ctx until its next qcat_batch_tsv_text), for callers that stay in HBM */
+void* qcat_ctx_tsv_text_devptr(qcat_ctx* ctx);
+
 /* the latest partition of this context: bin b = reads [bin_first[b], bin_first[b+1]) of `out`
  * (n_bins + 1 entries); source[i] = index in the input batch of read i of `out` (n_reads entries, may be NULL) */
 int  qcat_ctx_fetch_partition(qcat_ctx* ctx, uint64_t* bin_first, int32_t n_bins, uint32_t* source);

@@ -4,11 +4,13 @@
 // The functions are in batch_host.inc.  Included by qcat_hip.hip in front of middle_host.inc.
 #pragma once
 #include <memory>
+#include <vector>
 
 #include "../../include/qcat_hip.h"
 #include "dev_buf.h"
 #include "partition_core.h"
 #include "fqtext_core.h"
+#include "tsvtext_core.h"
 
 constexpr size_t BATCH_SLACK = 64;                 // bytes in front of and behind a batch's bases
 static_assert(BATCH_SLACK == qpart::PART_SLACK, "the partition's copy kernel relies on the batches' slack");
@@ -95,10 +97,27 @@ struct FqTextScratch {
     int32_t n_bins = 0;                        // 0: no demultiplexed text yet
     uint64_t total = 0;
 };
+// the TSV rows of a text batch (kernels_tsvtext.inc, tsvtext_host.inc), scratch of their own: the latest qcat_batch_tsv_text keeps
+// its text and row_first beside the latest demultiplexed text.  The tables' blob on the device and its host copy; the score part
+// of the kit with serial `score_kit` (0: none)
+struct TsvScratch {
+    qk::DevBuf<uint64_t> row_first, sums;
+    qk::DevBuf<uint32_t> name_len, keep, tile_first, bad;
+    qk::DevBuf<uint8_t> tables;
+    qk::DevBuf<uint8_t> out;                   // BATCH_SLACK in front of the text, like a batch's planes
+    qk::DevBuf<qcat_result> recs;              // records a caller handed over
+    std::vector<uint8_t> blob;
+    qtsv::ScoreTable scores;
+    uint64_t score_kit = 0;
+    uint32_t n_reads = 0;
+    bool valid = false;                        // false: no TSV text yet
+    uint64_t total = 0;
+};
 // what a context keeps for the batch functions
 struct BatchScratch {
     PartScratch part;
     FilterScratch filter;
     FqTextScratch fqtext;
+    TsvScratch tsv;
     qk::DevBuf<uint32_t> offs_bad;             // qcat_batch_from_device: the flag of k_offsets_check
 };

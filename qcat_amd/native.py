@@ -107,6 +107,35 @@ class DemuxOpts(C.Structure):
                 ("range_begin", C.c_uint64), ("range_end", C.c_uint64), ("input_fd", C.c_int32), ("rest_fd", C.c_int32)]
 
 
+class TsvNamesStruct(C.Structure):
+    """qcat_tsv_names (include/qcat_hip.h)"""
+    _fields_ = [("kit_name", C.POINTER(C.c_char_p)), ("bc_id", C.POINTER(C.POINTER(C.c_int32))), ("bc2_id", C.POINTER(C.POINTER(C.c_int32)))]
+
+
+class TsvNames(object):
+    """What the TSV rows of :meth:`NativeContext.tsv_text` print besides the bytes of the text: a ``qcat_tsv_names`` and the
+    buffers it points to, from the AdapterLayout list of the kit -- the kit's name (``None`` for a layout without one: simple
+    mode) and the Barcode ids of set 0 (``dual``: of set 1 as well) per template."""
+
+    def __init__(self, layouts, dual=False):
+        n_t = len(layouts)
+        self._kit_names = (C.c_char_p * max(1, n_t))(*[None if getattr(l, "kit", None) is None else str(l.kit).encode() for l in layouts])
+        self._bc_id = (C.POINTER(C.c_int32) * max(1, n_t))()
+        self._bc2_id = (C.POINTER(C.c_int32) * max(1, n_t))()
+        self._keep = []
+        for t, lay in enumerate(layouts):
+            s0 = lay.get_barcode_set(0) or []
+            s1 = (lay.get_barcode_set(1) or []) if dual else []
+            ids = (C.c_int32 * max(1, len(s0)))(*[int(b.id) for b in s0])
+            ids2 = (C.c_int32 * max(1, len(s1)))(*[int(b.id) for b in s1])
+            self._keep += [ids, ids2]
+            self._bc_id[t] = C.cast(ids, C.POINTER(C.c_int32))
+            self._bc2_id[t] = C.cast(ids2, C.POINTER(C.c_int32))
+        self.struct = TsvNamesStruct(kit_name=C.cast(self._kit_names, C.POINTER(C.c_char_p)),
+                                     bc_id=C.cast(self._bc_id, C.POINTER(C.POINTER(C.c_int32))),
+                                     bc2_id=C.cast(self._bc2_id, C.POINTER(C.POINTER(C.c_int32))) if dual else None)
+
+
 class DemuxStats(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_skipped", C.c_uint64), ("file_bytes", C.c_uint64),
                 ("parse_s", C.c_double), ("scan_s", C.c_double), ("write_s", C.c_double), ("total_s", C.c_double),
@@ -407,6 +436,9 @@ class HipLibrary(object):
             "qcat_batch_demux_text": (C.c_int, [vp, vp, vp, vp, u32, C.POINTER(C.c_uint64)]),
             "qcat_ctx_fetch_demux_text": (C.c_int, [vp, vp, C.c_uint64, vp, i32, vp, vp]),
             "qcat_ctx_demux_text_devptr": (vp, [vp]),
+            "qcat_batch_tsv_text": (C.c_int, [vp, vp, vp, vp, C.POINTER(TsvNamesStruct), u32, C.POINTER(C.c_uint64)]),
+            "qcat_ctx_fetch_tsv_text": (C.c_int, [vp, vp, C.c_uint64, vp]),
+            "qcat_ctx_tsv_text_devptr": (vp, [vp]),
             "qcat_ctx_partition_bins_devptr": (vp, [vp]),
             "qcat_ctx_partition_source_devptr": (vp, [vp]),
             "qcat_ctx_last_timing": (C.c_int, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
@@ -787,6 +819,14 @@ class DemuxText(object):
         self.text, self.bin_first_bytes, self.rec_first, self.source = text, bin_first_bytes, rec_first, source
 
 
+class TsvText(object):
+    """What :meth:`NativeContext.tsv_text` returns: ``text`` (bytes: the rows of the kept reads in read order, no header line) and
+    ``row_first`` (uint64, reads + 1 entries: row r is ``text[row_first[r]:row_first[r + 1]]``, empty for a dropped read)."""
+
+    def __init__(self, text, row_first):
+        self.text, self.row_first = text, row_first
+
+
 class NativeContext(object):
     """``qcat_ctx*`` handle: one device, one stream; not re-entrant."""
 
@@ -906,6 +946,28 @@ class NativeContext(object):
                                                               bin_first_bytes.ctypes.data, n_bins, rec_first.ctypes.data,
                                                               source.ctypes.data if n else None))
         return DemuxText(memoryview(text), bin_first_bytes, rec_first, source)
+
+    def tsv_text(self, kit, batch, names, records=None):
+        """qcat_batch_tsv_text of a batch made by :meth:`ResidentBatch.upload_fastq_text`: the driver's ``--tsv`` rows, formatted
+        on the device -- a :class:`TsvText`.  ``names``: a :class:`TsvNames` of the kit's layouts; ``records`` as in
+        :meth:`partition`."""
+        handle = kit.handle
+        last = getattr(self, "_resident_scan", None)
+        if records is None and last is not None and last[0] is kit:
+            handle = last[1]
+        if records is not None:
+            records = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
+            if len(records) != batch.n_reads:
+                raise RuntimeError("tsv_text: {} records for a batch of {} reads".format(len(records), batch.n_reads))
+        total = C.c_uint64()
+        self.hip.check(self.hip.lib.qcat_batch_tsv_text(self.handle, handle, batch.handle,
+                                                        records.ctypes.data if records is not None else None,
+                                                        C.byref(names.struct) if names is not None else None, 0, C.byref(total)))
+        text = np.empty(int(total.value), dtype=np.uint8)
+        row_first = np.zeros(batch.n_reads + 1, dtype=np.uint64)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_tsv_text(self.handle, text.ctypes.data if len(text) else None, len(text),
+                                                            row_first.ctypes.data))
+        return TsvText(text.tobytes(), row_first)
 
     def detect_kit(self, kit, bases, offsets):
         """per-template (votes, first voting read) of qcat_detect_kit."""

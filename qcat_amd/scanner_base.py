@@ -484,7 +484,31 @@ class BarcodeScanner(object):
         return kit, (lambda ctx, batch: ctx.scan_resident_batches(kit, batch, int(batch_size), kit_auto=kit_auto,
                                                                   filter_barcodes=bool(self.enable_filter_barcodes), fetch=False))
 
-    def demux_fastq_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None):
+    # the header line the reference driver prints in front of the rows of --tsv (qcat/cli.py:402)
+    TSV_HEADER = b"name\tlength\tbarcode\tscore\tkit\tadapter_end\tcomment\n"
+
+    def _tsv_names(self):
+        """what the TSV rows print per template, from the layouts of the scan's kit (as ``cli._native_demux`` builds the file
+        loop's tables): simple mode has its one list as the only template"""
+        layouts = [self._simple_layout] if self._native_mode == "simple" else self.layouts
+        return native.TsvNames(layouts, dual=self._native_mode == "dual")
+
+    def tsv_fastq_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None):
+        """The reference driver's ``--tsv`` output for FASTQ text: the bytes of a plain four-line FASTQ file go up, are parsed
+        and scanned on the device like :meth:`demux_fastq_text` does, and the table comes down -- the header line and one row
+        per kept read in read order, ``name length barcode score kit adapter_end comment`` (``qcat/cli.py:273-279`` behind
+        ``:514-534``), formatted on the device (qcat_batch_tsv_text).  Returns bytes.  No row is formatted here."""
+        kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
+        ctx = self._context()
+        batch = native.ResidentBatch.upload_fastq_text(ctx, text)
+        try:
+            scan(ctx, batch)
+            rows = ctx.tsv_text(kit, batch, self._tsv_names())
+        finally:
+            batch.destroy()
+        return self.TSV_HEADER + rows.text
+
+    def demux_fastq_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None, tsv=False):
         """:meth:`demux_batches` from FASTQ text to FASTQ text: the bytes of a plain four-line FASTQ file go up, are parsed on the
         device (qcat_batch_upload_fastq_text), scanned like :meth:`demux_batches` scans, and the bytes of every per-barcode
         ``.fastq`` file come down as the reference driver writes them (``qcat/cli.py:327-342`` behind ``:514-530``), formatted on
@@ -493,7 +517,8 @@ class BarcodeScanner(object):
         a call, nothing for reads the minimum-length filter drops.  Kits name the same id differently, so one bin is not always
         one file: the name of every record comes from its record (under a vote: of the kit its batch voted for); a bin with
         one name is sliced out whole, a bin with several record by record, in file order either way.  No record is formatted
-        here.  Text that is not plain: :class:`native.ResidentBatch.Unsupported`."""
+        here.  Text that is not plain: :class:`native.ResidentBatch.Unsupported`.  ``tsv=True``: ``(files, table)`` with the
+        bytes of :meth:`tsv_fastq_text` from the same upload and the same scan."""
         kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
         ctx = self._context()
         batch = native.ResidentBatch.upload_fastq_text(ctx, text)
@@ -501,6 +526,7 @@ class BarcodeScanner(object):
             n = batch.n_reads
             scan(ctx, batch)
             out = ctx.demux_text(kit, batch)
+            rows = ctx.tsv_text(kit, batch, self._tsv_names()) if tsv else None
             recs = np.zeros(n, dtype=native.RESULT_DTYPE)
             ctx.hip.check(ctx.hip.lib.qcat_ctx_fetch_results(ctx.handle, recs.ctypes.data, n))
         finally:
@@ -537,7 +563,8 @@ class BarcodeScanner(object):
             for u in ids[np.sort(np.unique(ids, return_index=True)[1])].tolist():   # the bin's names in order of appearance
                 files.setdefault(names[u], []).append(b"".join(out.text[rec_first[j]:rec_first[j + 1]]
                                                                for j in (np.flatnonzero(ids == u) + j0).tolist()))
-        return {name: b"".join(parts) for name, parts in files.items()}
+        files = {name: b"".join(parts) for name, parts in files.items()}
+        return (files, self.TSV_HEADER + rows.text) if tsv else files
 
     def _demux_resident(self, kit, read_sequences, read_qualities, scan):
         """upload, ``scan(ctx, batch)``, partition, and the bins as :meth:`demux_batch` returns them"""
