@@ -497,6 +497,18 @@ int  qcat_batch_devptrs(const qcat_batch* batch, const void** bases, const void*
  * Record count, line starts and every check are computed on the device; the host waits twice for eight bytes (the number of
  * lines, which sizes the tables; the verdict with the number of bases) and once for the bases' copy. */
 int  qcat_batch_upload_fastq_text(qcat_ctx* ctx, const uint8_t* text, uint64_t n_bytes, qcat_batch** out);
+/* The same with the reference driver's dispatch (qcat/cli.py:248-262): a first byte '>' means FASTA, anything else goes to exactly
+ * what qcat_batch_upload_fastq_text does.  A FASTA text gives the same kind of owned text batch: bases, offsets[n + 1], no quality
+ * plane, the text plane with the constants behind it, and a record per read with the title without '>', right-stripped, its tabs
+ * turned into blanks, and qual_off = 0.  Accepted is exactly what qcat_fastq_open accepts of a FASTA file: a '>' title line of
+ * the title class, ONE non-empty sequence line of bytes 0x21..0x7F with at most 2^31 - 1 bases, a next line that begins with '>'
+ * or the end of the text, a last record that may lack its newline.  Anything else -- a wrapped sequence, CRLF, a blank line, a
+ * FASTQ record in the middle --: QCAT_ERR_UNSUPPORTED with "not a plain two-line FASTA file (record N)", N the record
+ * qcat_fastq_open names for the same bytes (a record whose NEXT line lacks '>' is the one refused); no batch is left behind, the
+ * context stays usable.  The device passes are those of the FASTQ parse with a record pass of two lines per record. */
+int  qcat_batch_upload_text(qcat_ctx* ctx, const uint8_t* text, uint64_t n_bytes, qcat_batch** out);
+/* 1: the batch's text is FASTA, 0: FASTQ; a batch without a text plane: QCAT_ERR_ARG */
+int  qcat_batch_text_is_fasta(const qcat_batch* batch);
 /* the record table of a text batch, n_reads entries each (any array may be NULL): the counterpart of qcat_fastq_read_info.
  * A batch without a text plane: QCAT_ERR_ARG. */
 int  qcat_batch_fetch_text_records(qcat_ctx* ctx, const qcat_batch* batch, uint64_t* title_off, uint32_t* title_len,
@@ -511,7 +523,9 @@ int  qcat_batch_fetch_text_records(qcat_ctx* ctx, const qcat_batch* batch, uint6
  * writes nothing for it --, so the last bin is empty.  *n_text_bytes = the size of the text.
  * flags: reserved, must be 0.  A batch without a text plane: QCAT_ERR_ARG; 6 * n_reads >= 2^32: QCAT_ERR_UNSUPPORTED before
  * anything is enqueued.  Takes the scratch of qcat_batch_partition (the context's latest partition is gone afterwards).
- * Enqueues on the context's stream, synchronises once (the total).  The result is the same bytes run after run. */
+ * Enqueues on the context's stream, synchronises once (the total).  The result is the same bytes run after run.
+ * A FASTA text batch (qcat_batch_upload_text) gives the bytes of the per-barcode .fasta files, '>' title' '\n' seq[a:b] '\n' per
+ * kept read, in the same order with the same tables (qcat/cli.py:340-342). */
 int  qcat_batch_demux_text(qcat_ctx* ctx, const qcat_kit* kit, const qcat_batch* batch, const qcat_result* records,
                            uint32_t flags, uint64_t* n_text_bytes);
 /* the latest text of this context: text (cap >= its size), bin_first_bytes[n_bins + 1] (bin b = bytes [bin_first_bytes[b],
@@ -557,6 +571,30 @@ int  qcat_batch_tsv_text(qcat_ctx* ctx, const qcat_kit* kit, const qcat_batch* b
 int  qcat_ctx_fetch_tsv_text(qcat_ctx* ctx, uint8_t* text, uint64_t cap, uint64_t* row_first);
 /* the text in device memory (owned by ctx until its next qcat_batch_tsv_text), for callers that stay in HBM */
 void* qcat_ctx_tsv_text_devptr(qcat_ctx* ctx);
+
+/* ---- the driver's annotated single stream of a text batch, assembled in device memory ----
+ * What the reference driver writes without -b and without --tsv (qcat/cli.py:345-358), for a FASTQ or a FASTA text batch by the
+ * calls of `records` (as in qcat_batch_tsv_text: NULL = this context's latest resident scan of these reads with `kit`): ONE
+ * device buffer, owned by ctx until its next call of this function, with the kept reads in READ order -- byte for byte what
+ * qcat_fastq_demux writes to out_fd for the same file, kit and options:
+ *   sigil title sep "barcode=" id '\n' seq[a:b] "\n+\n" qual[a:b] '\n'       FASTQ
+ *   sigil title sep "barcode=" id '\n' seq[a:b] '\n'                         FASTA
+ * sigil = the byte in front of the stored title, sep = one blank when the stored title holds a blank and two when it holds none
+ * (name + " " + comment + " barcode="), id = str(Barcode.id) of a called read (dual mode: id "/" id2; "called" as in
+ * qcat_batch_tsv_text) and "none" of any other read.  The kept slice [a:b) and the dropped reads are the partition's; a dropped
+ * read contributes 0 bytes.  The ids come from `names` (kit_name is not looked at).
+ * flags: reserved, must be 0.  QCAT_ERR_ARG, the context stays usable: a batch without a text plane, NULL `names` or a NULL id
+ * table in it, records == NULL without a matching scan.  10 * n_reads >= 2^32: QCAT_ERR_UNSUPPORTED.  All before anything is
+ * enqueued.  Uses scratch of its own: a context keeps its demultiplexed text, its TSV text and its stream side by side.
+ * Enqueues on the context's stream, synchronises once (the total).  The result is the same bytes run after run.
+ * *n_text_bytes = the size of the stream. */
+int  qcat_batch_annot_text(qcat_ctx* ctx, const qcat_kit* kit, const qcat_batch* batch, const qcat_result* records,
+                           const qcat_tsv_names* names, uint32_t flags, uint64_t* n_text_bytes);
+/* the latest stream of this context: text (cap >= its size) and rec_first[n_reads + 1] (record r = bytes [rec_first[r],
+ * rec_first[r+1]), empty for a dropped read).  Either may be NULL. */
+int  qcat_ctx_fetch_annot_text(qcat_ctx* ctx, uint8_t* text, uint64_t cap, uint64_t* rec_first);
+/* the stream in device memory (owned by ctx until its next qcat_batch_annot_text), for callers that stay in HBM */
+void* qcat_ctx_annot_text_devptr(qcat_ctx* ctx);
 
 /* the latest partition of this context: bin b = reads [bin_first[b], bin_first[b+1]) of `out`
  * (n_bins + 1 entries); source[i] = index in the input batch of read i of `out` (n_reads entries, may be NULL) */

@@ -31,6 +31,7 @@ struct qcat_batch {
     uint8_t* text = nullptr;
     uint64_t text_bytes = 0;
     qfq::Rec* text_recs = nullptr;
+    bool text_fasta = false;       // the text is FASTA (qcat_batch_upload_text): two lines per record, qual_off = 0, no quality part
 
     // the planes of a batch that owns its memory (fixed size, the caller's: no generation bump); a view -- the device buffers
     // belong to a context (host-buffer calls) or a pipeline stage -- leaves them empty, and destroying it frees the shell only
@@ -113,11 +114,27 @@ struct TsvScratch {
     bool valid = false;                        // false: no TSV text yet
     uint64_t total = 0;
 };
+// the annotated single stream of a text batch (kernels_textstream.inc, textstream_host.inc), scratch of its own beside the
+// demultiplexed text and the TSV text: the segment table, the stream and rec_first of the latest qcat_batch_annot_text; the tag
+// plane on the device (BATCH_SLACK, the TSV tables' blob, the stream's constants, BATCH_SLACK) and the host copy it was uploaded
+// from
+struct AnnotScratch {
+    qk::DevBuf<uint64_t> seg_off, seg_src, sums, rec_first;
+    qk::DevBuf<uint32_t> chunk_first;
+    qk::DevBuf<uint8_t> tags;
+    qk::DevBuf<uint8_t> out;                   // BATCH_SLACK in front of the text, like a batch's planes
+    qk::DevBuf<qcat_result> recs;              // records a caller handed over
+    std::vector<uint8_t> plane;
+    uint32_t n_reads = 0;
+    bool valid = false;                        // false: no stream yet
+    uint64_t total = 0;
+};
 // what a context keeps for the batch functions
 struct BatchScratch {
     PartScratch part;
     FilterScratch filter;
     FqTextScratch fqtext;
     TsvScratch tsv;
+    AnnotScratch annot;
     qk::DevBuf<uint32_t> offs_bad;             // qcat_batch_from_device: the flag of k_offsets_check
 };

@@ -1,7 +1,8 @@
 // fqtext_core.h -- the lane arithmetic of FASTQ text in device memory (kernels_fqtext.inc), as pure functions that compile for
 // host and device: the blocks a text is cut into, the newline and byte-class masks of a 16-byte vector, the rank of a newline
 // inside its wave, the checks of one four-line record against the line table, and the segment table of one output record.
-// tests/fqtext_check.cpp runs the passes' block and lane schedule through these on the host.
+// tests/fqtext_check.cpp runs the passes' block and lane schedule through these on the host.  The two-line FASTA form of the
+// record checks and segments stands at the end of the file (tests/textstream_check.cpp).
 //
 // Vocabulary.  The TEXT is n_bytes bytes of a FASTQ file.  LINE k begins at line_start[k] and ends in front of its '\n' (the
 // last line may have none); a text has n_lines = newlines + (1 when its last byte is no newline) lines, and
@@ -172,5 +173,57 @@ QP_HD void record_segments(const Rec& r, uint64_t s, uint64_t keep, bool skipped
 // an upper bound of the output text of n reads parsed from n_bytes of text: a record of the text has at least
 // 1 + title + 1 + seq + 3 + seq bytes, a record of the output at most 1 + title + 2 + seq + 3 + seq + 1
 QP_HD uint64_t output_bound(uint64_t n_bytes, uint64_t n) { return n_bytes + 2 * n + 1; }
+
+// ---- FASTA text: '>' title line and ONE sequence line per record (fa_parse, fastq_host.inc) -------------------------------------
+// The line table is the same -- the kind of line k is k mod 2, and lines_bad picks the byte class by the kind's parity, which is
+// that of k mod 4 --, RECORD r is lines 2 r and 2 r + 1.  fa_parse fails record r when the line BEHIND its sequence does not begin
+// with '>' (a wrapped sequence, a blank line, a FASTQ record in the middle), so the lane of a record looks at two things and
+// blames two records: its own first line without '>' lowers the bad line to FA_FRONT -- the sequence line of the record in front
+// of it --, a missing or empty or overlong sequence line and an overlong title to FA_SELF, its own title line.  The first record
+// fa_parse refuses is (the smallest lowered line) / 2: every record in front of it has exactly two lines, so the lines 2 r are
+// their titles; no lane r' <= r finds its first line without '>' (record r' - 1 passed the check of the line behind it, and
+// the text's first byte is '>'), the byte classes flag nothing below line 2 r, and each of fa_parse's reasons for r lowers line
+// 2 r or 2 r + 1: a title line without newline or nothing behind it (r has one line), an empty or overlong sequence, a title
+// too long (FA_SELF); a byte outside a line's class (k_fq_lines, line 2 r or 2 r + 1); a line behind the sequence that does
+// not begin with '>' (lane r + 1, which exists because that line does: FA_FRONT of r + 1 = 2 r + 1).
+enum : uint32_t { FA_OK = 0, FA_SELF = 1, FA_FRONT = 2 };
+QP_HD uint64_t fa_records_of(uint64_t n_lines) { return (n_lines + 1) / 2; }
+// the line a lane with verdict v (not FA_OK) lowers the status to
+QP_HD uint64_t fa_blamed_line(uint64_t r, uint32_t v) { return v == FA_FRONT && r ? 2 * r - 1 : 2 * r; }
+// the 1-based record the host names for a lowered line
+QP_HD uint64_t fa_record_of_line(uint64_t bad_line) { return bad_line / 2 + 1; }
+
+// ls[0..2]: the starts of the record's two lines and of the line behind them (ls[2] is not read when the record has one line);
+// lines: 1 or 2, the lines the text holds of this record
+template <class Byte>
+QP_HD uint32_t fa_record_of(const Byte& at, const uint64_t* ls, uint32_t lines, Rec* r) {
+    const uint64_t l0 = ls[0], l1 = ls[1];
+    if (at(l0) != '>') return FA_FRONT;                                        // (an empty line: its first byte is its '\n')
+    if (lines < 2) return FA_SELF;
+    const uint64_t l2 = ls[2];
+    const uint64_t sl = l2 - l1 - 1;
+    if (sl == 0 || sl > 0x7FFFFFFFull) return FA_SELF;
+    uint64_t tl = l1 - l0 - 2;                                                 // the title line without '>'
+    while (tl && is_blank(at(l0 + tl))) --tl;
+    if (tl > 0xFFFFFFFFull) return FA_SELF;
+    uint32_t blank = 0;
+    for (uint64_t i = 0; i < tl; ++i) blank |= is_blank(at(l0 + 1 + i)) ? 1u : 0u;
+    r->title_off = l0 + 1; r->title_len = (uint32_t)tl;
+    r->seq_off = l1; r->seq_len = (uint32_t)sl;
+    r->qual_off = 0;
+    r->title_blank = blank; r->pad = 0;
+    return FA_OK;
+}
+
+// one output record of a FASTA batch: '>' title' '\n' seq[s : s + keep] '\n' -- the sigil is the byte in front of the stored
+// title --, in the six segments of record_segments with the two of the quality part empty
+QP_HD void fa_record_segments(const Rec& r, uint64_t s, uint64_t keep, bool skipped, uint64_t const_off, uint64_t* len, uint64_t* src) {
+    for (uint32_t i = 0; i < FQ_SEGS; ++i) { len[i] = 0; src[i] = 0; }
+    if (skipped) return;
+    len[0] = 1 + (uint64_t)r.title_len; src[0] = r.title_off - 1;
+    len[1] = r.title_blank ? 1 : 2;     src[1] = const_off + (r.title_blank ? FQ_C_NL : FQ_C_BLANK_NL);
+    len[2] = keep;                      src[2] = r.seq_off + s;
+    len[5] = 1;                         src[5] = const_off + FQ_C_LAST_NL;
+}
 
 }  // namespace qfq

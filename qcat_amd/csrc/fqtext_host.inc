@@ -2,8 +2,11 @@
 //   qcat_batch_upload_fastq_text   the bytes of a FASTQ file go up; a resident batch with bases, offsets, a text plane and a record
 //                                  table comes out of four device passes -- count, lines, records, the bases' copy -- with the
 //                                  verdict of fq_parse (fastq_host.inc) on every record
+//   qcat_batch_upload_text         the driver's dispatch by the first byte: '>' is FASTA -- the same passes with k_fa_records
+//                                  (kernels_textstream.inc) and two lines per record --, anything else the call above
 //   qcat_batch_demux_text          the per-barcode FASTQ files' bytes of a scanned text batch: the partition's keys and order, a
-//                                  segment table of six byte ranges per read, the partition's scan chain and copy kernel
+//                                  segment table of six byte ranges per read (a FASTA batch: k_fa_segments, the .fasta files'
+//                                  bytes), the partition's scan chain and copy kernel
 //   qcat_ctx_fetch_demux_text / _demux_text_devptr / qcat_batch_fetch_text_records   read-out
 // Included by qcat_hip.hip behind batch_host.inc: it uses that file's helpers and the partition's phases.
 
@@ -11,10 +14,13 @@ static int fq_text_refused(uint64_t record) {
     return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_upload_fastq_text: not a plain four-line FASTQ file (record " + std::to_string(record) + ")");
 }
 
-extern "C" int qcat_batch_upload_fastq_text(qcat_ctx* c, const uint8_t* text, uint64_t n_bytes, qcat_batch** out) {
-    if (!c || !out || (!text && n_bytes)) return set_err(QCAT_ERR_ARG, "qcat_batch_upload_fastq_text: null argument");
-    if (n_bytes && text[0] == '>')
-        return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_upload_fastq_text: FASTA text is not supported, the text must be FASTQ (record 1)");
+static int fa_text_refused(uint64_t record) {
+    return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_upload_text: not a plain two-line FASTA file (record " + std::to_string(record) + ")");
+}
+
+// the parse of both formats: `fasta` -- two lines per record, k_fa_records and its blame rule (fqtext_core.h) -- or FASTQ; fn: the
+// entry point's name in front of the messages
+static int text_upload(qcat_ctx* c, const uint8_t* text, uint64_t n_bytes, qcat_batch** out, bool fasta, const std::string& fn) {
     HIPCHK(hipSetDevice(c->device));
     FqTextScratch& T = c->batch.fqtext;
     BatchPtr b(new qcat_batch());
@@ -25,6 +31,7 @@ extern "C" int qcat_batch_upload_fastq_text(qcat_ctx* c, const uint8_t* text, ui
         return set_err(QCAT_ERR_NOMEM, "hipMalloc failed for the text plane");
     b->text = b->store.text + BATCH_SLACK;
     b->text_bytes = n_bytes;
+    b->text_fasta = fasta;
     uint8_t tail[qfq::FQ_CONST_BYTES + BATCH_SLACK];
     memset(tail, 0, sizeof tail);
     qfq::fq_constants(tail);
@@ -35,7 +42,7 @@ extern "C" int qcat_batch_upload_fastq_text(qcat_ctx* c, const uint8_t* text, ui
     if (c->timing) HIPCHK_DRAIN(c->stream, hipEventRecord(c->ev[0], c->stream));
     // a. newlines per block, their scan; the host sizes the line table by the total
     const uint64_t n_blocks = qfq::blocks_of(n_bytes);
-    if (n_blocks >= (1ull << 31)) { (void)hipStreamSynchronize(c->stream); return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_upload_fastq_text: text too large (>= 2^45 bytes)"); }
+    if (n_blocks >= (1ull << 31)) { (void)hipStreamSynchronize(c->stream); return set_err(QCAT_ERR_UNSUPPORTED, fn + ": text too large (>= 2^45 bytes)"); }
     uint64_t newlines = 0;
     if (n_blocks) {
         if ((rc = grow(T.counts, (size_t)n_blocks + 1)) || (rc = grow(T.sums, part_scan_sums(n_blocks + 1)))) { (void)hipStreamSynchronize(c->stream); return rc; }
@@ -44,10 +51,10 @@ extern "C" int qcat_batch_upload_fastq_text(qcat_ctx* c, const uint8_t* text, ui
         mark(c, "fq_count");
         HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&newlines, T.counts + n_blocks, 8, hipMemcpyDeviceToHost, c->stream));
     }
-    if ((rc = stream_done(c, "qcat_batch_upload_fastq_text"))) return rc;
+    if ((rc = stream_done(c, fn.c_str()))) return rc;
     const uint64_t n_lines = n_bytes ? qfq::lines_of(newlines, text[n_bytes - 1] == '\n') : 0;
-    const uint64_t n_rec64 = qfq::records_of(n_lines);
-    if (n_rec64 >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_upload_fastq_text: more than 2^31 records in one text");
+    const uint64_t n_rec64 = fasta ? qfq::fa_records_of(n_lines) : qfq::records_of(n_lines);
+    if (n_rec64 >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, fn + ": more than 2^31 records in one text");
     const uint32_t n = (uint32_t)n_rec64;
     // b. line table and byte classes; c. records, their lengths' scan = the offsets
     if ((rc = grow(T.line_start, (size_t)newlines + 2)) || (rc = grow(T.status, 1)) || (rc = grow(T.seq_src, n)) ||
@@ -61,18 +68,20 @@ extern "C" int qcat_batch_upload_fastq_text(qcat_ctx* c, const uint8_t* text, ui
     if (n_blocks) hipLaunchKernelGGL(k_fq_lines, dim3((uint32_t)n_blocks), dim3(256), 0, c->stream, (const uint8_t*)b->text, n_bytes,
                                      (const uint64_t*)T.counts.get(), n_blocks, T.line_start.get(), status);
     mark(c, "fq_lines");
-    hipLaunchKernelGGL(k_fq_records, dim3(n / 256 + 1), dim3(256), 0, c->stream, b->text, (const uint64_t*)T.line_start.get(), n_lines, n,
-                       b->text_recs, offsets, T.seq_src.get(), status);
+    if (fasta) hipLaunchKernelGGL(k_fa_records, dim3(n / 256 + 1), dim3(256), 0, c->stream, b->text, (const uint64_t*)T.line_start.get(), n_lines, n,
+                                  b->text_recs, offsets, T.seq_src.get(), status);
+    else hipLaunchKernelGGL(k_fq_records, dim3(n / 256 + 1), dim3(256), 0, c->stream, b->text, (const uint64_t*)T.line_start.get(), n_lines, n,
+                            b->text_recs, offsets, T.seq_src.get(), status);
     part_scan_launch<uint64_t>(offsets, (uint64_t)n + 1, T.sums, c->stream);
     mark(c, "fq_records");
     uint64_t back[2] = {0, 0};                                 // status, number of bases
     HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&back[0], status, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&back[1], offsets + n, 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = stream_done(c, "qcat_batch_upload_fastq_text"))) return rc;
-    if (back[0] != qfq::FQ_NO_LINE) return fq_text_refused(back[0] / 4 + 1);
+    if ((rc = stream_done(c, fn.c_str()))) return rc;
+    if (back[0] != qfq::FQ_NO_LINE) return fasta ? fa_text_refused(qfq::fa_record_of_line(back[0])) : fq_text_refused(back[0] / 4 + 1);
     // d. the bases: the partition's copy over the text plane, segment r = the sequence line of read r
     b->n_reads = n; b->n_bases = back[1];
-    if (b->n_bases > n_bytes) return set_err(QCAT_ERR_DEVICE, "qcat_batch_upload_fastq_text: more bases than text");
+    if (b->n_bases > n_bytes) return set_err(QCAT_ERR_DEVICE, fn + ": more bases than text");
     if (!b->alloc(false)) return set_err(QCAT_ERR_NOMEM, "hipMalloc failed for batch");
     const uint64_t chunks = qpart::chunks_of(b->n_bases);
     if ((rc = grow(T.chunk_first, (size_t)chunks + 1))) return rc;
@@ -84,9 +93,29 @@ extern "C" int qcat_batch_upload_fastq_text(qcat_ctx* c, const uint8_t* text, ui
                            (const uint8_t*)nullptr, (uint8_t*)nullptr);
     }
     mark(c, "fq_bases");
-    if ((rc = stream_done(c, "qcat_batch_upload_fastq_text"))) return rc;
+    if ((rc = stream_done(c, fn.c_str()))) return rc;
     *out = b.release();
     return 0;
+}
+
+extern "C" int qcat_batch_upload_fastq_text(qcat_ctx* c, const uint8_t* text, uint64_t n_bytes, qcat_batch** out) {
+    if (!c || !out || (!text && n_bytes)) return set_err(QCAT_ERR_ARG, "qcat_batch_upload_fastq_text: null argument");
+    if (n_bytes && text[0] == '>')
+        return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_upload_fastq_text: FASTA text is not supported, the text must be FASTQ (record 1)");
+    return text_upload(c, text, n_bytes, out, false, "qcat_batch_upload_fastq_text");
+}
+
+// the driver's dispatch (qcat/cli.py:248-262): a first byte '>' is FASTA, anything else goes the FASTQ way
+extern "C" int qcat_batch_upload_text(qcat_ctx* c, const uint8_t* text, uint64_t n_bytes, qcat_batch** out) {
+    if (!c || !out || (!text && n_bytes)) return set_err(QCAT_ERR_ARG, "qcat_batch_upload_text: null argument");
+    if (n_bytes && text[0] == '>') return text_upload(c, text, n_bytes, out, true, "qcat_batch_upload_text");
+    return qcat_batch_upload_fastq_text(c, text, n_bytes, out);
+}
+
+extern "C" int qcat_batch_text_is_fasta(const qcat_batch* b) {
+    if (!b) return set_err(QCAT_ERR_ARG, "qcat_batch_text_is_fasta: null batch");
+    if (!b->text) return set_err(QCAT_ERR_ARG, "qcat_batch_text_is_fasta: the batch has no text plane");
+    return b->text_fasta ? 1 : 0;
 }
 
 extern "C" int qcat_batch_fetch_text_records(qcat_ctx* c, const qcat_batch* b, uint64_t* title_off, uint32_t* title_len,
@@ -161,6 +190,11 @@ extern "C" int qcat_batch_demux_text(qcat_ctx* c, const qcat_kit* ckit, const qc
     part_order(c, j);
     if (n) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(T.source, j.source, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
     hipLaunchKernelGGL(k_part_bins, dim3(j.n_bins / 256 + 1), dim3(256), 0, c->stream, j.key_sorted, n, j.n_bins, P.bins.get());
+    if (b->text_fasta)
+        hipLaunchKernelGGL(k_fa_segments, dim3(n / 256 + 1), dim3(256), 0, c->stream, (const uint32_t*)j.source, j.key_sorted,
+                           (const uint64_t*)P.start.get(), (const uint64_t*)P.keep.get(), (const uint64_t*)b->offsets, (const qfq::Rec*)b->text_recs, n,
+                           j.n_bins - 1, b->text_bytes, T.seg_off.get(), T.seg_src.get());
+    else
     hipLaunchKernelGGL(k_fq_segments, dim3(n / 256 + 1), dim3(256), 0, c->stream, (const uint32_t*)j.source, j.key_sorted,
                        (const uint64_t*)P.start.get(), (const uint64_t*)P.keep.get(), (const uint64_t*)b->offsets, (const qfq::Rec*)b->text_recs, n,
                        j.n_bins - 1, b->text_bytes, T.seg_off.get(), T.seg_src.get());

@@ -40,6 +40,7 @@
 #include "kernels_partition.inc"
 #include "kernels_fqtext.inc"
 #include "kernels_tsvtext.inc"
+#include "kernels_textstream.inc"
 #include "kernels_filter.inc"
 #include "static_registry.inc"
 #include "pipeline.h"
@@ -1261,6 +1262,8 @@ extern "C" int qcat_sg_align(qcat_ctx* c, const uint8_t* queries, const uint64_t
 #include "fastq_stream.inc"
 // the driver's TSV rows of a scanned text batch, formatted in device memory (the score texts: fq_repr_double of fastq_host.inc)
 #include "tsvtext_host.inc"
+// the driver's annotated single stream of a scanned text batch (the id texts: the id slots of the TSV tables)
+#include "textstream_host.inc"
 
 // ------------------------------------------------------------------------------------------
 // multi-GPU count reduction (RCCL)

@@ -206,6 +206,11 @@ QP_HD uint64_t title_bound(uint64_t text_bytes, uint64_t n_bases, uint64_t n) {
     const uint64_t rest = 2 * n_bases + 6 * n;
     return text_bytes + 1 > rest ? text_bytes + 1 - rest : 0;
 }
+// the same for FASTA text: a record has at least '>' title '\n' seq '\n' = title + seq + 3 bytes
+QP_HD uint64_t fa_title_bound(uint64_t text_bytes, uint64_t n_bases, uint64_t n) {
+    const uint64_t rest = n_bases + 3 * n;
+    return text_bytes + 1 > rest ? text_bytes + 1 - rest : 0;
+}
 // name + comment <= title + 4 ("None"), three separators around them, a kept length of at most 10 digits, and the longer of the
 // two middles with its separators: "none\t-1\tnone\t-1" or id "/" id2, score, kit, an adapter_end of at most 11 characters
 QP_HD uint64_t row_const(const Tables& T) {

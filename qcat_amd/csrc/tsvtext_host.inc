@@ -73,7 +73,8 @@ extern "C" int qcat_batch_tsv_text(qcat_ctx* c, const qcat_kit* ckit, const qcat
     const std::string err = qtsv::tables_build(simple, dual, (uint32_t)d.nt, n_ids, ids, names->kit_name, S.scores, &blob, &T, &den_off);
     if (!err.empty()) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_tsv_text: " + err);
     const uint32_t n = b->n_reads;
-    const uint64_t bound = qtsv::output_bound(qtsv::title_bound(b->text_bytes, b->n_bases, n), n, T);
+    const uint64_t titles = b->text_fasta ? qtsv::fa_title_bound(b->text_bytes, b->n_bases, n) : qtsv::title_bound(b->text_bytes, b->n_bases, n);
+    const uint64_t bound = qtsv::output_bound(titles, n, T);
     const uint64_t max_tiles = qtsv::tiles_of(bound);
     if (max_tiles >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_tsv_text: text too large (>= 2^45 bytes)");
     HIPCHK(hipSetDevice(c->device));

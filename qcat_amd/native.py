@@ -439,6 +439,11 @@ class HipLibrary(object):
             "qcat_batch_tsv_text": (C.c_int, [vp, vp, vp, vp, C.POINTER(TsvNamesStruct), u32, C.POINTER(C.c_uint64)]),
             "qcat_ctx_fetch_tsv_text": (C.c_int, [vp, vp, C.c_uint64, vp]),
             "qcat_ctx_tsv_text_devptr": (vp, [vp]),
+            "qcat_batch_upload_text": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(vp)]),
+            "qcat_batch_text_is_fasta": (C.c_int, [vp]),
+            "qcat_batch_annot_text": (C.c_int, [vp, vp, vp, vp, C.POINTER(TsvNamesStruct), u32, C.POINTER(C.c_uint64)]),
+            "qcat_ctx_fetch_annot_text": (C.c_int, [vp, vp, C.c_uint64, vp]),
+            "qcat_ctx_annot_text_devptr": (vp, [vp]),
             "qcat_ctx_partition_bins_devptr": (vp, [vp]),
             "qcat_ctx_partition_source_devptr": (vp, [vp]),
             "qcat_ctx_last_timing": (C.c_int, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
@@ -692,16 +697,35 @@ class ResidentBatch(object):
     def upload_fastq_text(cls, ctx, text):
         """qcat_batch_upload_fastq_text: the bytes of a FASTQ file, parsed on the device into a batch with bases, offsets, a text
         plane and a record table (:meth:`text_records`); :class:`ResidentBatch.Unsupported` when the text is not plain"""
+        return cls._upload_text(ctx, text, "qcat_batch_upload_fastq_text")
+
+    @classmethod
+    def upload_text(cls, ctx, text):
+        """qcat_batch_upload_text: :meth:`upload_fastq_text` with the reference driver's dispatch -- a first byte ``>`` means a
+        plain two-line FASTA file (:attr:`is_fasta`), anything else FASTQ; :class:`ResidentBatch.Unsupported` when the text is
+        not plain"""
+        return cls._upload_text(ctx, text, "qcat_batch_upload_text")
+
+    @classmethod
+    def _upload_text(cls, ctx, text, entry):
         hip = HipLibrary.get()
         if isinstance(text, str):
             text = text.encode("latin-1")
         buf = np.frombuffer(text, dtype=np.uint8)
         h = C.c_void_p()
-        rc = hip.lib.qcat_batch_upload_fastq_text(ctx.handle, buf.ctypes.data if len(buf) else None, len(buf), C.byref(h))
+        rc = getattr(hip.lib, entry)(ctx.handle, buf.ctypes.data if len(buf) else None, len(buf), C.byref(h))
         if rc == -2:
             raise cls.Unsupported("qcat_hip error -2: " + (hip.lib.qcat_last_error() or b"").decode("utf-8", "replace"))
         hip.check(rc)
         return cls(ctx, h)
+
+    @property
+    def is_fasta(self):
+        """the batch's text is FASTA (RuntimeError for a batch without a text plane)"""
+        rc = self.hip.lib.qcat_batch_text_is_fasta(self.handle)
+        if rc < 0:
+            self.hip.check(rc)
+        return bool(rc)
 
     def text_records(self):
         """qcat_batch_fetch_text_records: (title_off uint64, title_len uint32, seq_off uint64, seq_len uint32), one entry per read"""
@@ -827,6 +851,14 @@ class TsvText(object):
         self.text, self.row_first = text, row_first
 
 
+class AnnotText(object):
+    """What :meth:`NativeContext.annot_text` returns: ``text`` (bytes: the annotated records of the kept reads in read order) and
+    ``rec_first`` (uint64, reads + 1 entries: record r is ``text[rec_first[r]:rec_first[r + 1]]``, empty for a dropped read)."""
+
+    def __init__(self, text, rec_first):
+        self.text, self.rec_first = text, rec_first
+
+
 class NativeContext(object):
     """``qcat_ctx*`` handle: one device, one stream; not re-entrant."""
 
@@ -924,8 +956,8 @@ class NativeContext(object):
         return Partition(part, bin_first, source)
 
     def demux_text(self, kit, batch, records=None):
-        """qcat_batch_demux_text of a batch made by :meth:`ResidentBatch.upload_fastq_text`: the bytes of the per-barcode FASTQ
-        files, formatted on the device -- a :class:`DemuxText`.  ``records`` as in :meth:`partition`."""
+        """qcat_batch_demux_text of a batch made by :meth:`ResidentBatch.upload_fastq_text` or :meth:`~ResidentBatch.upload_text`:
+        the bytes of the per-barcode FASTQ files (FASTA files of a FASTA batch), formatted on the device -- a :class:`DemuxText`.  ``records`` as in :meth:`partition`."""
         handle = kit.handle
         last = getattr(self, "_resident_scan", None)
         if records is None and last is not None and last[0] is kit:
@@ -968,6 +1000,28 @@ class NativeContext(object):
         self.hip.check(self.hip.lib.qcat_ctx_fetch_tsv_text(self.handle, text.ctypes.data if len(text) else None, len(text),
                                                             row_first.ctypes.data))
         return TsvText(text.tobytes(), row_first)
+
+    def annot_text(self, kit, batch, names, records=None):
+        """qcat_batch_annot_text of a batch made by :meth:`ResidentBatch.upload_text`: the driver's single output stream -- every
+        kept read in read order with `` barcode=<id>`` behind its title --, assembled on the device: an :class:`AnnotText`.
+        ``names``: a :class:`TsvNames` of the kit's layouts; ``records`` as in :meth:`partition`."""
+        handle = kit.handle
+        last = getattr(self, "_resident_scan", None)
+        if records is None and last is not None and last[0] is kit:
+            handle = last[1]
+        if records is not None:
+            records = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
+            if len(records) != batch.n_reads:
+                raise RuntimeError("annot_text: {} records for a batch of {} reads".format(len(records), batch.n_reads))
+        total = C.c_uint64()
+        self.hip.check(self.hip.lib.qcat_batch_annot_text(self.handle, handle, batch.handle,
+                                                          records.ctypes.data if records is not None else None,
+                                                          C.byref(names.struct) if names is not None else None, 0, C.byref(total)))
+        text = np.empty(int(total.value), dtype=np.uint8)
+        rec_first = np.zeros(batch.n_reads + 1, dtype=np.uint64)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_annot_text(self.handle, text.ctypes.data if len(text) else None, len(text),
+                                                              rec_first.ctypes.data))
+        return AnnotText(text.tobytes(), rec_first)
 
     def detect_kit(self, kit, bases, offsets):
         """per-template (votes, first voting read) of qcat_detect_kit."""

@@ -473,7 +473,7 @@ class BarcodeScanner(object):
         return self._demux_resident(kit, read_sequences, read_qualities, scan)
 
     def _batches_scan(self, batch_size, trim, min_read_length, qcat_config):
-        """the kit and the resident scan of :meth:`demux_batches` and :meth:`demux_fastq_text`: ``scan(ctx, batch)`` with the
+        """the kit and the resident scan of :meth:`demux_batches` and the ``*_text`` methods: ``scan(ctx, batch)`` with the
         driver's per-batch semantics -- the vote of a scanner with several kits, the barcode filter"""
         if qcat_config is None:
             qcat_config = config.qcatConfig()
@@ -498,15 +498,38 @@ class BarcodeScanner(object):
         and scanned on the device like :meth:`demux_fastq_text` does, and the table comes down -- the header line and one row
         per kept read in read order, ``name length barcode score kit adapter_end comment`` (``qcat/cli.py:273-279`` behind
         ``:514-534``), formatted on the device (qcat_batch_tsv_text).  Returns bytes.  No row is formatted here."""
+        return self._tsv_text(native.ResidentBatch.upload_fastq_text, text, batch_size, trim, min_read_length, qcat_config)
+
+    def tsv_fastx_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None):
+        """:meth:`tsv_fastq_text` with the reference driver's dispatch by the first byte (qcat_batch_upload_text): a plain two-line
+        FASTA file gives the same table as its FASTQ twin."""
+        return self._tsv_text(native.ResidentBatch.upload_text, text, batch_size, trim, min_read_length, qcat_config)
+
+    def _tsv_text(self, upload, text, batch_size, trim, min_read_length, qcat_config):
         kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
         ctx = self._context()
-        batch = native.ResidentBatch.upload_fastq_text(ctx, text)
+        batch = upload(ctx, text)
         try:
             scan(ctx, batch)
             rows = ctx.tsv_text(kit, batch, self._tsv_names())
         finally:
             batch.destroy()
         return self.TSV_HEADER + rows.text
+
+    def annot_fastx_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None):
+        """The reference driver's default product for FASTQ or FASTA text (``qcat/cli.py:345-358``: no ``-b``, no ``--tsv``): the
+        bytes go up, are parsed (qcat_batch_upload_text) and scanned on the device like :meth:`demux_fastq_text` does, and ONE
+        stream comes down -- every kept read in read order with `` barcode=<id>`` behind its title --, assembled on the device
+        (qcat_batch_annot_text).  Returns bytes.  No record is formatted here."""
+        kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
+        ctx = self._context()
+        batch = native.ResidentBatch.upload_text(ctx, text)
+        try:
+            scan(ctx, batch)
+            out = ctx.annot_text(kit, batch, self._tsv_names())
+        finally:
+            batch.destroy()
+        return out.text
 
     def demux_fastq_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None, tsv=False):
         """:meth:`demux_batches` from FASTQ text to FASTQ text: the bytes of a plain four-line FASTQ file go up, are parsed on the
@@ -519,11 +542,20 @@ class BarcodeScanner(object):
         one name is sliced out whole, a bin with several record by record, in file order either way.  No record is formatted
         here.  Text that is not plain: :class:`native.ResidentBatch.Unsupported`.  ``tsv=True``: ``(files, table)`` with the
         bytes of :meth:`tsv_fastq_text` from the same upload and the same scan."""
+        return self._demux_text(native.ResidentBatch.upload_fastq_text, text, batch_size, trim, min_read_length, qcat_config, tsv)
+
+    def demux_fastx_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None, tsv=False):
+        """:meth:`demux_fastq_text` with the reference driver's dispatch by the first byte (qcat_batch_upload_text): a plain two-line
+        FASTA file gives the bytes of the per-barcode ``.fasta`` files (``qcat/cli.py:318-323``, ``:340-342``)."""
+        return self._demux_text(native.ResidentBatch.upload_text, text, batch_size, trim, min_read_length, qcat_config, tsv)
+
+    def _demux_text(self, upload, text, batch_size, trim, min_read_length, qcat_config, tsv):
         kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
         ctx = self._context()
-        batch = native.ResidentBatch.upload_fastq_text(ctx, text)
+        batch = upload(ctx, text)
         try:
             n = batch.n_reads
+            ext = "fasta" if batch.is_fasta else "fastq"
             scan(ctx, batch)
             out = ctx.demux_text(kit, batch)
             rows = ctx.tsv_text(kit, batch, self._tsv_names()) if tsv else None
@@ -547,7 +579,7 @@ class BarcodeScanner(object):
                 bc_id = d["barcode"].name
                 if bc_id:
                     bc_id = bc_id.replace("/", "_")
-            name = "{}.fastq".format(bc_id)
+            name = "{}.{}".format(bc_id, ext)
             if name not in names:
                 names.append(name)
             name_index.append(names.index(name))
