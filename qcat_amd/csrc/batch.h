@@ -1,7 +1,8 @@
 // batch.h -- the resident batch (reads in device memory) and what belongs to it on the host (host only, like dev_buf.h): the
 // type behind qcat_batch*, its two makers' building blocks -- an owned batch allocates its planes, a view borrows a context's
-// staging -- the guard of a batch under construction, and the scratch of qcat_batch_partition / qcat_batch_from_device.
-// The functions are in batch_host.inc.  Included by qcat_hip.hip in front of middle_host.inc.
+// staging -- the guard of a batch under construction, and the scratch of the calls over a batch: the partition, the filter, the
+// text parse and the three text products (their shared types: text_out.h).  The functions are in batch_host.inc and the host
+// files named at each scratch.  Included by qcat_hip.hip in front of middle_host.inc.
 #pragma once
 #include <memory>
 #include <vector>
@@ -11,6 +12,7 @@
 #include "partition_core.h"
 #include "fqtext_core.h"
 #include "tsvtext_core.h"
+#include "text_out.h"
 
 constexpr size_t BATCH_SLACK = 64;                 // bytes in front of and behind a batch's bases
 static_assert(BATCH_SLACK == qpart::PART_SLACK, "the partition's copy kernel relies on the batches' slack");
@@ -74,7 +76,6 @@ using BatchPtr = std::unique_ptr<qcat_batch, BatchDeleter>;
 struct PartScratch {
     qk::DevBuf<uint32_t> key[2], idx[2], hist, sums32, chunk_first;
     qk::DevBuf<uint64_t> start, keep, src_pos, sums64, bins;
-    qk::DevBuf<qcat_result> recs;              // records a caller handed over
     uint32_t* source = nullptr;                // = idx[passes & 1] of the latest partition
     uint32_t n_reads = 0;
     int32_t n_bins = 0;                        // 0: no partition yet
@@ -86,48 +87,35 @@ struct FilterScratch {
     qk::DevBuf<qcat_result> recs;
 };
 // FASTQ text on the device (kernels_fqtext.inc, fqtext_host.inc): the parse's block counts, line table, status and copy tables;
-// the segment table, the arrays and the text of the latest qcat_batch_demux_text (`source`: a copy of the partition scratch's
-// sorted order, which the next partition overwrites)
+// the segment table, the text of the latest qcat_batch_demux_text (text.first: the first byte of every record in sorted order)
+// and its arrays of its own (`source`: a copy of the partition scratch's sorted order, which the next partition overwrites)
 struct FqTextScratch {
     qk::DevBuf<uint64_t> counts, sums, line_start, seq_src, status;
     qk::DevBuf<uint32_t> chunk_first;
-    qk::DevBuf<uint64_t> seg_off, seg_src, rec_first, bin_bytes;
-    qk::DevBuf<uint8_t> out;                   // BATCH_SLACK in front of the text, like a batch's planes
+    qk::DevBuf<uint64_t> seg_off, seg_src, bin_bytes;
     qk::DevBuf<uint32_t> source;
-    uint32_t n_reads = 0;
-    int32_t n_bins = 0;                        // 0: no demultiplexed text yet
-    uint64_t total = 0;
+    TextOut text;
+    int32_t n_bins = 0;                        // bins of `text`
 };
 // the TSV rows of a text batch (kernels_tsvtext.inc, tsvtext_host.inc), scratch of their own: the latest qcat_batch_tsv_text keeps
-// its text and row_first beside the latest demultiplexed text.  The tables' blob on the device and its host copy; the score part
-// of the kit with serial `score_kit` (0: none)
+// its text (text.first: the rows) beside the latest demultiplexed text.  The tables' blob on the device beside its host copy;
+// the score part of the kit with serial `score_kit` (0: none)
 struct TsvScratch {
-    qk::DevBuf<uint64_t> row_first, sums;
+    qk::DevBuf<uint64_t> sums;
     qk::DevBuf<uint32_t> name_len, keep, tile_first, bad;
-    qk::DevBuf<uint8_t> tables;
-    qk::DevBuf<uint8_t> out;                   // BATCH_SLACK in front of the text, like a batch's planes
-    qk::DevBuf<qcat_result> recs;              // records a caller handed over
-    std::vector<uint8_t> blob;
+    MirroredTable tables;
+    TextOut text;
     qtsv::ScoreTable scores;
     uint64_t score_kit = 0;
-    uint32_t n_reads = 0;
-    bool valid = false;                        // false: no TSV text yet
-    uint64_t total = 0;
 };
 // the annotated single stream of a text batch (kernels_textstream.inc, textstream_host.inc), scratch of its own beside the
-// demultiplexed text and the TSV text: the segment table, the stream and rec_first of the latest qcat_batch_annot_text; the tag
-// plane on the device (BATCH_SLACK, the TSV tables' blob, the stream's constants, BATCH_SLACK) and the host copy it was uploaded
-// from
+// demultiplexed text and the TSV text: the segment table and the stream of the latest qcat_batch_annot_text (text.first: the
+// records); the tag plane (BATCH_SLACK, the TSV tables' blob, the stream's constants, BATCH_SLACK) on the device beside its host copy
 struct AnnotScratch {
-    qk::DevBuf<uint64_t> seg_off, seg_src, sums, rec_first;
+    qk::DevBuf<uint64_t> seg_off, seg_src, sums;
     qk::DevBuf<uint32_t> chunk_first;
-    qk::DevBuf<uint8_t> tags;
-    qk::DevBuf<uint8_t> out;                   // BATCH_SLACK in front of the text, like a batch's planes
-    qk::DevBuf<qcat_result> recs;              // records a caller handed over
-    std::vector<uint8_t> plane;
-    uint32_t n_reads = 0;
-    bool valid = false;                        // false: no stream yet
-    uint64_t total = 0;
+    MirroredTable tags;
+    TextOut text;
 };
 // what a context keeps for the batch functions
 struct BatchScratch {
@@ -136,5 +124,6 @@ struct BatchScratch {
     FqTextScratch fqtext;
     TsvScratch tsv;
     AnnotScratch annot;
+    qk::DevBuf<qcat_result> recs;              // records a caller handed over, of whichever call runs (records_on_device, text_out_host.inc)
     qk::DevBuf<uint32_t> offs_bad;             // qcat_batch_from_device: the flag of k_offsets_check
 };

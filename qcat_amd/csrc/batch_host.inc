@@ -317,15 +317,15 @@ struct PartJob {
     uint32_t* source;
 };
 
+// what the partition shares with the text products of a batch (text_out_host.inc)
+static int batch_call_check(const qcat_ctx* c, const qcat_kit* ckit, const qcat_batch* b, const qcat_result* records, uint32_t flags,
+                            const void* out, const std::string& fn, const char* text_maker);
+static int records_on_device(qcat_ctx* c, const qcat_result* records, uint32_t n, const qcat_result** recs);
+
 static int part_check(const qcat_ctx* c, const qcat_kit* ckit, const qcat_batch* b, const qcat_result* records, uint32_t flags, qcat_batch** out) {
-    if (!c || !ckit || !b || !out) return set_err(QCAT_ERR_ARG, "qcat_batch_partition: null argument");
-    if (flags != 0) return set_err(QCAT_ERR_ARG, "qcat_batch_partition: flags are reserved and must be 0");
-    if (b->device != c->device) return set_err(QCAT_ERR_ARG, "qcat_batch_partition: batch lives on another device than the context");
+    if (int rc = batch_call_check(c, ckit, b, records, flags, out, "qcat_batch_partition", nullptr)) return rc;
     if (b->true_len || !b->owned())
         return set_err(QCAT_ERR_ARG, "qcat_batch_partition: the batch holds read windows or borrowed buffers, not whole reads of its own");
-    if (!records && (c->last_kit != ckit || c->last_n_reads != b->n_reads))
-        return set_err(QCAT_ERR_ARG, "qcat_batch_partition: records == NULL needs this context's latest qcat_scan_resident to be a scan of "
-                                     "these reads with this kit");
     if (records && !part_records_fit(ckit->hk.dk, records, b->n_reads))
         return set_err(QCAT_ERR_ARG, "qcat_batch_partition: a record indexes outside the kit's templates / barcode sets or has a negative trim");
     if ((size_t)b->n_reads + 1 >= (1ull << 31)) return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_partition: batch too large (>= 2^31 reads)");
@@ -346,13 +346,7 @@ static int part_size_buffers(qcat_ctx* c, PartJob& j, const qcat_result* records
     if ((rc = grow(P.src_pos, n))) return rc;
     if ((rc = grow(P.bins, (size_t)j.n_bins + 1))) return rc;
     if ((rc = grow(P.chunk_first, (size_t)j.max_chunks + 1))) return rc;
-    j.recs = c->results;
-    if (records) {
-        if ((rc = grow(P.recs, n))) return rc;
-        if (n) HIPCHK(hipMemcpyAsync(P.recs, records, (size_t)n * sizeof(qcat_result), hipMemcpyHostToDevice, c->stream));
-        j.recs = P.recs;
-    }
-    return 0;
+    return records_on_device(c, records, n, &j.recs);
 }
 
 // a. keys
@@ -441,7 +435,7 @@ extern "C" int qcat_batch_partition(qcat_ctx* c, const qcat_kit* ckit, const qca
     P.n_bins = 0; P.source = nullptr;                        // (a failure below leaves no partition behind)
     if ((rc = part_size_buffers(c, j, records))) return rc;
     timing_slot(c);
-    if (c->timing) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    if (c->timing) HIPCHK_DRAIN(c->stream, hipEventRecord(c->ev[0], c->stream));     // (the caller's records may be on their way)
     part_keys(c, j);
     part_order(c, j);
     part_offsets(c, j);

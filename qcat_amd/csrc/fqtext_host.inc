@@ -8,7 +8,9 @@
 //                                  segment table of six byte ranges per read (a FASTA batch: k_fa_segments, the .fasta files'
 //                                  bytes), the partition's scan chain and copy kernel
 //   qcat_ctx_fetch_demux_text / _demux_text_devptr / qcat_batch_fetch_text_records   read-out
-// Included by qcat_hip.hip behind batch_host.inc: it uses that file's helpers and the partition's phases.
+// The demultiplexed text's argument check, its tail and its read-out are the text products' shared layer (text_out_host.inc);
+// here are its bounds, its own arrays (bin_bytes, source) and its launches.
+// Included by qcat_hip.hip behind batch_host.inc and text_out_host.inc: it uses their helpers and the partition's phases.
 
 static int fq_text_refused(uint64_t record) {
     return set_err(QCAT_ERR_UNSUPPORTED, "qcat_batch_upload_fastq_text: not a plain four-line FASTQ file (record " + std::to_string(record) + ")");
@@ -139,13 +141,7 @@ extern "C" int qcat_batch_fetch_text_records(qcat_ctx* c, const qcat_batch* b, u
 // per-barcode FASTQ text of a scanned text batch
 // ------------------------------------------------------------------------------------------
 static int fq_demux_check(const qcat_ctx* c, const qcat_kit* ckit, const qcat_batch* b, const qcat_result* records, uint32_t flags, const uint64_t* n_text_bytes) {
-    if (!c || !ckit || !b || !n_text_bytes) return set_err(QCAT_ERR_ARG, "qcat_batch_demux_text: null argument");
-    if (flags != 0) return set_err(QCAT_ERR_ARG, "qcat_batch_demux_text: flags are reserved and must be 0");
-    if (b->device != c->device) return set_err(QCAT_ERR_ARG, "qcat_batch_demux_text: batch lives on another device than the context");
-    if (!b->text || !b->owned()) return set_err(QCAT_ERR_ARG, "qcat_batch_demux_text: the batch has no text plane (qcat_batch_upload_fastq_text makes one)");
-    if (!records && (c->last_kit != ckit || c->last_n_reads != b->n_reads))
-        return set_err(QCAT_ERR_ARG, "qcat_batch_demux_text: records == NULL needs this context's latest qcat_scan_resident to be a scan of "
-                                     "these reads with this kit");
+    if (int rc = batch_call_check(c, ckit, b, records, flags, n_text_bytes, "qcat_batch_demux_text", "qcat_batch_upload_fastq_text")) return rc;
     if (records && !part_records_fit(ckit->hk.dk, records, b->n_reads))
         return set_err(QCAT_ERR_ARG, "qcat_batch_demux_text: a record indexes outside the kit's templates / barcode sets or has a negative trim");
     if ((uint64_t)qfq::FQ_SEGS * b->n_reads >= (1ull << 32))
@@ -174,16 +170,16 @@ extern "C" int qcat_batch_demux_text(qcat_ctx* c, const qcat_kit* ckit, const qc
     PartScratch& P = c->batch.part;
     FqTextScratch& T = c->batch.fqtext;
     P.n_bins = 0; P.source = nullptr;                        // (the partition's scratch is taken: no partition is left behind)
-    T.n_bins = 0;
+    T.text.valid = false;
     const uint32_t n = j.n, n_segs = qfq::FQ_SEGS * n;
     if ((rc = part_size_buffers(c, j, records))) return rc;
     if ((rc = grow(T.seg_off, (size_t)n_segs + 1)) || (rc = grow(T.seg_src, n_segs)) || (rc = grow(T.sums, part_scan_sums((uint64_t)n_segs + 1))) ||
-        (rc = grow(T.rec_first, (size_t)n + 1)) || (rc = grow(T.bin_bytes, (size_t)j.n_bins + 1)) || (rc = grow(T.out, bound + 2 * BATCH_SLACK)) ||
+        (rc = grow(T.text.first, (size_t)n + 1)) || (rc = grow(T.bin_bytes, (size_t)j.n_bins + 1)) || (rc = grow(T.text.buf, bound + 2 * BATCH_SLACK)) ||
         (rc = grow(T.source, n))) {
         (void)hipStreamSynchronize(c->stream);               // (the caller's records may be on their way)
         return rc;
     }
-    uint8_t* const dst = T.out + BATCH_SLACK;
+    uint8_t* const dst = text_out_ptr(T.text);
     timing_slot(c);
     if (c->timing) HIPCHK_DRAIN(c->stream, hipEventRecord(c->ev[0], c->stream));
     part_keys(c, j);
@@ -200,7 +196,7 @@ extern "C" int qcat_batch_demux_text(qcat_ctx* c, const qcat_kit* ckit, const qc
                        j.n_bins - 1, b->text_bytes, T.seg_off.get(), T.seg_src.get());
     part_scan_launch<uint64_t>(T.seg_off, (uint64_t)n_segs + 1, T.sums, c->stream);
     hipLaunchKernelGGL(k_fq_firsts, dim3(std::max(n, j.n_bins) / 256 + 1), dim3(256), 0, c->stream, (const uint64_t*)T.seg_off.get(), n,
-                       (const uint64_t*)P.bins.get(), j.n_bins, T.rec_first.get(), T.bin_bytes.get());
+                       (const uint64_t*)P.bins.get(), j.n_bins, T.text.first.get(), T.bin_bytes.get());
     hipLaunchKernelGGL(k_part_chunks, dim3((uint32_t)((j.max_chunks + 255) / 256)), dim3(256), 0, c->stream, (const uint64_t*)T.seg_off.get(), n_segs,
                        P.chunk_first.get(), j.max_chunks);
     mark(c, "text_segments");
@@ -208,28 +204,22 @@ extern "C" int qcat_batch_demux_text(qcat_ctx* c, const qcat_kit* ckit, const qc
                        (const uint64_t*)T.seg_src.get(), n_segs, (const uint32_t*)P.chunk_first.get(), (const uint8_t*)b->text, dst,
                        (const uint8_t*)nullptr, (uint8_t*)nullptr);
     mark(c, "text_copy");
-    uint64_t total = 0;
-    HIPCHK_DRAIN(c->stream, hipMemcpyAsync(&total, T.seg_off + n_segs, 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = stream_done(c, "qcat_batch_demux_text"))) return rc;
-    if (total > bound) return set_err(QCAT_ERR_DEVICE, "qcat_batch_demux_text: the text is longer than its bound");
-    T.n_reads = n; T.n_bins = (int32_t)j.n_bins; T.total = total;
-    *n_text_bytes = total;
-    return 0;
+    T.n_bins = (int32_t)j.n_bins;
+    return text_out_finish(c, T.text, T.seg_off + n_segs, n, bound, "qcat_batch_demux_text", n_text_bytes);
 }
 
 extern "C" int qcat_ctx_fetch_demux_text(qcat_ctx* c, uint8_t* text, uint64_t cap, uint64_t* bin_first_bytes, int32_t n_bins,
                                          uint64_t* rec_first, uint32_t* source) {
-    if (!c) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_demux_text: null context");
-    const FqTextScratch& T = c->batch.fqtext;
-    if (!T.n_bins) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_demux_text: no demultiplexed text on this context");
-    if (text && cap < T.total) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_demux_text: the buffer is shorter than the text");
-    if (bin_first_bytes && n_bins != T.n_bins) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_demux_text: bin count does not match the latest text");
+    const FqTextScratch* T = c ? &c->batch.fqtext : nullptr;
+    int rc = text_out_fetch_check(c, T ? &T->text : nullptr, text, cap, "qcat_ctx_fetch_demux_text", "no demultiplexed text");
+    if (rc) return rc;
+    if (bin_first_bytes && n_bins != T->n_bins) return set_err(QCAT_ERR_ARG, "qcat_ctx_fetch_demux_text: bin count does not match the latest text");
     HIPCHK(hipSetDevice(c->device));
-    if (text && T.total) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(text, T.out + BATCH_SLACK, T.total, hipMemcpyDeviceToHost, c->stream));
-    if (bin_first_bytes) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(bin_first_bytes, T.bin_bytes, ((size_t)T.n_bins + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (rec_first) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(rec_first, T.rec_first, ((size_t)T.n_reads + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (source && T.n_reads) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(source, T.source, (size_t)T.n_reads * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = text_out_fetch_copies(c, T->text, text, nullptr))) return rc;                     // (the copies in the order they always had)
+    if (bin_first_bytes) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(bin_first_bytes, T->bin_bytes, ((size_t)T->n_bins + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = text_out_fetch_copies(c, T->text, nullptr, rec_first))) return rc;
+    if (source && T->text.n_reads) HIPCHK_DRAIN(c->stream, hipMemcpyAsync(source, T->source, (size_t)T->text.n_reads * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
-extern "C" void* qcat_ctx_demux_text_devptr(qcat_ctx* c) { return c && c->batch.fqtext.n_bins ? (void*)(c->batch.fqtext.out + BATCH_SLACK) : nullptr; }
+extern "C" void* qcat_ctx_demux_text_devptr(qcat_ctx* c) { return text_out_devptr(c ? &c->batch.fqtext.text : nullptr); }

@@ -1034,6 +1034,8 @@ extern "C" int qcat_ctx_last_timing(qcat_ctx* c, const char** names, float* ms, 
 #include "batch_host.inc"
 // --filter-barcodes on the device: filter_run for the records of a scan, qcat_filter_barcodes for records of a caller
 #include "filter_host.inc"
+// what the calls over a scanned batch share: argument check, records, name tables, mirrored tables, the finished text
+#include "text_out_host.inc"
 // FASTQ text in device memory: the parse into a resident batch, per-barcode FASTQ text out of one (kernels_fqtext.inc)
 #include "fqtext_host.inc"
 // the kit vote: VoteBuf and vote_enqueue, and the entry points that vote -- qcat_detect_kit, the kit-auto host-buffer calls,

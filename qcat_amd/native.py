@@ -933,21 +933,33 @@ class NativeContext(object):
                                                          int(batch_reads)))
         return out
 
+    def _kit_and_records(self, method, kit, batch, records):
+        """(kit handle, records pointer) of a call over a scanned batch: without ``records`` the handle the context's latest
+        resident scan ran with -- the voted kit's -- and a null pointer, else the caller's records as a contiguous array (the
+        pointer keeps it alive)"""
+        last = getattr(self, "_resident_scan", None)
+        if records is None:
+            return (last[1] if last is not None and last[0] is kit else kit.handle), None
+        records = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
+        if len(records) != batch.n_reads:
+            raise RuntimeError("{}: {} records for a batch of {} reads".format(method, len(records), batch.n_reads))
+        return kit.handle, records.ctypes.data_as(C.c_void_p)
+
+    def _fetch_text(self, total, n_reads, fetch):
+        """room for the ``total`` bytes a text call reported and for its n_reads + 1 first bytes, filled by
+        ``fetch(text pointer, capacity, first-bytes pointer)``: the product's qcat_ctx_fetch_*_text"""
+        text = np.empty(int(total.value), dtype=np.uint8)
+        first = np.zeros(n_reads + 1, dtype=np.uint64)
+        self.hip.check(fetch(text.ctypes.data if len(text) else None, len(text), first.ctypes.data))
+        return text, first
+
     def partition(self, kit, batch, records=None):
         """qcat_batch_partition: the reads of ``batch`` grouped by barcode -- a :class:`Partition`.  ``records``: a RESULT_DTYPE
         array with one record per read, or None for the records of this context's latest :meth:`scan_resident` or
         :meth:`scan_resident_batches` (of ``batch`` with ``kit``)."""
-        handle = kit.handle
-        last = getattr(self, "_resident_scan", None)
-        if records is None and last is not None and last[0] is kit:
-            handle = last[1]
-        if records is not None:
-            records = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
-            if len(records) != batch.n_reads:
-                raise RuntimeError("partition: {} records for a batch of {} reads".format(len(records), batch.n_reads))
+        handle, recs = self._kit_and_records("partition", kit, batch, records)
         out = C.c_void_p()
-        self.hip.check(self.hip.lib.qcat_batch_partition(self.handle, handle, batch.handle,
-                                                         records.ctypes.data if records is not None else None, 0, C.byref(out)))
+        self.hip.check(self.hip.lib.qcat_batch_partition(self.handle, handle, batch.handle, recs, 0, C.byref(out)))
         part = ResidentBatch(self, out)
         n_bins = self.hip.lib.qcat_kit_partition_bins(handle)
         bin_first = np.zeros(n_bins + 1, dtype=np.uint64)
@@ -958,69 +970,36 @@ class NativeContext(object):
     def demux_text(self, kit, batch, records=None):
         """qcat_batch_demux_text of a batch made by :meth:`ResidentBatch.upload_fastq_text` or :meth:`~ResidentBatch.upload_text`:
         the bytes of the per-barcode FASTQ files (FASTA files of a FASTA batch), formatted on the device -- a :class:`DemuxText`.  ``records`` as in :meth:`partition`."""
-        handle = kit.handle
-        last = getattr(self, "_resident_scan", None)
-        if records is None and last is not None and last[0] is kit:
-            handle = last[1]
-        if records is not None:
-            records = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
-            if len(records) != batch.n_reads:
-                raise RuntimeError("demux_text: {} records for a batch of {} reads".format(len(records), batch.n_reads))
+        handle, recs = self._kit_and_records("demux_text", kit, batch, records)
         total = C.c_uint64()
-        self.hip.check(self.hip.lib.qcat_batch_demux_text(self.handle, handle, batch.handle,
-                                                          records.ctypes.data if records is not None else None, 0, C.byref(total)))
+        self.hip.check(self.hip.lib.qcat_batch_demux_text(self.handle, handle, batch.handle, recs, 0, C.byref(total)))
         n, n_bins = batch.n_reads, self.hip.lib.qcat_kit_partition_bins(handle)
-        text = np.empty(int(total.value), dtype=np.uint8)
         bin_first_bytes = np.zeros(n_bins + 1, dtype=np.uint64)
-        rec_first = np.zeros(n + 1, dtype=np.uint64)
         source = np.zeros(n, dtype=np.uint32)
-        self.hip.check(self.hip.lib.qcat_ctx_fetch_demux_text(self.handle, text.ctypes.data if len(text) else None, len(text),
-                                                              bin_first_bytes.ctypes.data, n_bins, rec_first.ctypes.data,
-                                                              source.ctypes.data if n else None))
+        text, rec_first = self._fetch_text(total, n, lambda t, cap, first: self.hip.lib.qcat_ctx_fetch_demux_text(
+            self.handle, t, cap, bin_first_bytes.ctypes.data, n_bins, first, source.ctypes.data if n else None))
         return DemuxText(memoryview(text), bin_first_bytes, rec_first, source)
 
     def tsv_text(self, kit, batch, names, records=None):
         """qcat_batch_tsv_text of a batch made by :meth:`ResidentBatch.upload_fastq_text`: the driver's ``--tsv`` rows, formatted
         on the device -- a :class:`TsvText`.  ``names``: a :class:`TsvNames` of the kit's layouts; ``records`` as in
         :meth:`partition`."""
-        handle = kit.handle
-        last = getattr(self, "_resident_scan", None)
-        if records is None and last is not None and last[0] is kit:
-            handle = last[1]
-        if records is not None:
-            records = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
-            if len(records) != batch.n_reads:
-                raise RuntimeError("tsv_text: {} records for a batch of {} reads".format(len(records), batch.n_reads))
+        handle, recs = self._kit_and_records("tsv_text", kit, batch, records)
         total = C.c_uint64()
-        self.hip.check(self.hip.lib.qcat_batch_tsv_text(self.handle, handle, batch.handle,
-                                                        records.ctypes.data if records is not None else None,
+        self.hip.check(self.hip.lib.qcat_batch_tsv_text(self.handle, handle, batch.handle, recs,
                                                         C.byref(names.struct) if names is not None else None, 0, C.byref(total)))
-        text = np.empty(int(total.value), dtype=np.uint8)
-        row_first = np.zeros(batch.n_reads + 1, dtype=np.uint64)
-        self.hip.check(self.hip.lib.qcat_ctx_fetch_tsv_text(self.handle, text.ctypes.data if len(text) else None, len(text),
-                                                            row_first.ctypes.data))
+        text, row_first = self._fetch_text(total, batch.n_reads, lambda t, cap, first: self.hip.lib.qcat_ctx_fetch_tsv_text(self.handle, t, cap, first))
         return TsvText(text.tobytes(), row_first)
 
     def annot_text(self, kit, batch, names, records=None):
         """qcat_batch_annot_text of a batch made by :meth:`ResidentBatch.upload_text`: the driver's single output stream -- every
         kept read in read order with `` barcode=<id>`` behind its title --, assembled on the device: an :class:`AnnotText`.
         ``names``: a :class:`TsvNames` of the kit's layouts; ``records`` as in :meth:`partition`."""
-        handle = kit.handle
-        last = getattr(self, "_resident_scan", None)
-        if records is None and last is not None and last[0] is kit:
-            handle = last[1]
-        if records is not None:
-            records = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
-            if len(records) != batch.n_reads:
-                raise RuntimeError("annot_text: {} records for a batch of {} reads".format(len(records), batch.n_reads))
+        handle, recs = self._kit_and_records("annot_text", kit, batch, records)
         total = C.c_uint64()
-        self.hip.check(self.hip.lib.qcat_batch_annot_text(self.handle, handle, batch.handle,
-                                                          records.ctypes.data if records is not None else None,
+        self.hip.check(self.hip.lib.qcat_batch_annot_text(self.handle, handle, batch.handle, recs,
                                                           C.byref(names.struct) if names is not None else None, 0, C.byref(total)))
-        text = np.empty(int(total.value), dtype=np.uint8)
-        rec_first = np.zeros(batch.n_reads + 1, dtype=np.uint64)
-        self.hip.check(self.hip.lib.qcat_ctx_fetch_annot_text(self.handle, text.ctypes.data if len(text) else None, len(text),
-                                                              rec_first.ctypes.data))
+        text, rec_first = self._fetch_text(total, batch.n_reads, lambda t, cap, first: self.hip.lib.qcat_ctx_fetch_annot_text(self.handle, t, cap, first))
         return AnnotText(text.tobytes(), rec_first)
 
     def detect_kit(self, kit, bases, offsets):

@@ -8,6 +8,7 @@ the mapping of native index records back to ``Barcode`` / ``AdapterLayout`` obje
 per-read work of ``detect_barcode`` (``:521-604``) -- windows, adapter and barcode alignments,
 thresholds, conflict detection, trims -- happens inside one native call per batch.
 """
+import contextlib
 import logging
 import operator
 
@@ -505,15 +506,22 @@ class BarcodeScanner(object):
         FASTA file gives the same table as its FASTQ twin."""
         return self._tsv_text(native.ResidentBatch.upload_text, text, batch_size, trim, min_read_length, qcat_config)
 
-    def _tsv_text(self, upload, text, batch_size, trim, min_read_length, qcat_config):
+    @contextlib.contextmanager
+    def _scanned_text(self, upload, text, batch_size, trim, min_read_length, qcat_config):
+        """the frame of the ``*_text`` methods: ``text`` goes up through ``upload`` and is scanned (:meth:`_batches_scan`); the
+        body gets ``(ctx, kit, batch)`` and the batch is destroyed behind it"""
         kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
         ctx = self._context()
         batch = upload(ctx, text)
         try:
             scan(ctx, batch)
-            rows = ctx.tsv_text(kit, batch, self._tsv_names())
+            yield ctx, kit, batch
         finally:
             batch.destroy()
+
+    def _tsv_text(self, upload, text, batch_size, trim, min_read_length, qcat_config):
+        with self._scanned_text(upload, text, batch_size, trim, min_read_length, qcat_config) as (ctx, kit, batch):
+            rows = ctx.tsv_text(kit, batch, self._tsv_names())
         return self.TSV_HEADER + rows.text
 
     def annot_fastx_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None):
@@ -521,14 +529,8 @@ class BarcodeScanner(object):
         bytes go up, are parsed (qcat_batch_upload_text) and scanned on the device like :meth:`demux_fastq_text` does, and ONE
         stream comes down -- every kept read in read order with `` barcode=<id>`` behind its title --, assembled on the device
         (qcat_batch_annot_text).  Returns bytes.  No record is formatted here."""
-        kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
-        ctx = self._context()
-        batch = native.ResidentBatch.upload_text(ctx, text)
-        try:
-            scan(ctx, batch)
+        with self._scanned_text(native.ResidentBatch.upload_text, text, batch_size, trim, min_read_length, qcat_config) as (ctx, kit, batch):
             out = ctx.annot_text(kit, batch, self._tsv_names())
-        finally:
-            batch.destroy()
         return out.text
 
     def demux_fastq_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None, tsv=False):
@@ -550,19 +552,13 @@ class BarcodeScanner(object):
         return self._demux_text(native.ResidentBatch.upload_text, text, batch_size, trim, min_read_length, qcat_config, tsv)
 
     def _demux_text(self, upload, text, batch_size, trim, min_read_length, qcat_config, tsv):
-        kit, scan = self._batches_scan(batch_size, trim, min_read_length, qcat_config)
-        ctx = self._context()
-        batch = upload(ctx, text)
-        try:
+        with self._scanned_text(upload, text, batch_size, trim, min_read_length, qcat_config) as (ctx, kit, batch):
             n = batch.n_reads
             ext = "fasta" if batch.is_fasta else "fastq"
-            scan(ctx, batch)
             out = ctx.demux_text(kit, batch)
             rows = ctx.tsv_text(kit, batch, self._tsv_names()) if tsv else None
             recs = np.zeros(n, dtype=native.RESULT_DTYPE)
             ctx.hip.check(ctx.hip.lib.qcat_ctx_fetch_results(ctx.handle, recs.ctypes.data, n))
-        finally:
-            batch.destroy()
         rec_first = out.rec_first.astype(np.int64)
         bin_bytes = out.bin_first_bytes.astype(np.int64)
         kept = int(np.count_nonzero(np.diff(rec_first)))                         # (skipped reads: the last bin, 0 bytes each)

@@ -16,21 +16,10 @@
 #include <vector>
 
 #include "fqtext_core.h"
+#include "check_common.h"
 
 using namespace qfq;
 using qpart::Vec16;
-
-static uint64_t g_rng = 1;
-static uint64_t rnd() {                                   // SplitMix64
-    uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint64_t rnd_below(uint64_t n) { return n ? rnd() % n : 0; }
-
-struct Section { const char* name; uint64_t cases = 0, bad = 0; };
-static void report(const Section& s) { printf("%s: %llu cases, %llu mismatches\n", s.name, (unsigned long long)s.cases, (unsigned long long)s.bad); }
 
 // ---- the expected values: a sequential parser (the rules of fq_parse, restated byte by byte) ----------------------------------------
 struct Want { std::vector<Rec> recs; uint64_t bad_record = 0; };     // bad_record: 1-based, 0 = the text is plain
@@ -71,32 +60,23 @@ static Want sequential(const std::string& t) {
 }
 
 // ---- the text plane as the device holds it: slack, text, constants, slack ----------------------------------------------------------
-struct Plane {
-    std::vector<uint8_t> mem;
+struct TextPlane : Plane {
     uint64_t n_bytes;
-    uint64_t stray = 0;                                    // loads outside the allocation or unaligned
-    explicit Plane(const std::string& t) : mem(t.size() + FQ_CONST_BYTES + 2 * qpart::PART_SLACK, 0xA5), n_bytes(t.size()) {
-        if (!t.empty()) memcpy(mem.data() + qpart::PART_SLACK, t.data(), t.size());
-        uint8_t tail[FQ_CONST_BYTES + qpart::PART_SLACK];
-        memset(tail, 0, sizeof tail);
-        fq_constants(tail);
-        memcpy(mem.data() + qpart::PART_SLACK + t.size(), tail, sizeof tail);
+    static std::vector<uint8_t> payload(const std::string& t) {
+        std::vector<uint8_t> p(t.size() + FQ_CONST_BYTES, 0);
+        if (!t.empty()) memcpy(p.data(), t.data(), t.size());
+        fq_constants(p.data() + t.size());
+        return p;
     }
-    uint8_t* text() { return mem.data() + qpart::PART_SLACK; }
-    Vec16 load16(int64_t a) {
-        Vec16 v; v.w[0] = v.w[1] = v.w[2] = v.w[3] = 0;
-        // (the plane's own start is 16-byte aligned on the device: offsets from the text count)
-        if ((a & 15) != 0 || a < -(int64_t)qpart::PART_SLACK || a + 16 > (int64_t)(mem.size() - qpart::PART_SLACK)) { ++stray; return v; }
-        memcpy(v.w, text() + a, 16);
-        return v;
-    }
+    explicit TextPlane(const std::string& t) : Plane(payload(t)), n_bytes(t.size()) {}
+    uint8_t* text() { return at0(); }
 };
 static uint32_t valid_of(uint64_t off, uint64_t n_bytes) { return off >= n_bytes ? 0u : (n_bytes - off >= FQ_VEC ? 0xFFFFu : below((uint32_t)(n_bytes - off))); }
 
 struct Parsed { std::vector<Rec> recs; std::vector<uint64_t> offsets, seq_src; uint64_t bad_line = FQ_NO_LINE; uint64_t faults = 0; uint64_t n_lines = 0; };
 
 // k_fq_count, the scan, k_fq_lines, k_fq_records and the scan of the lengths
-static Parsed device_parse(Plane& pl) {
+static Parsed device_parse(TextPlane& pl) {
     Parsed out;
     const uint64_t n_bytes = pl.n_bytes, n_blocks = blocks_of(n_bytes);
     std::vector<uint64_t> first(n_blocks + 1, 0);
@@ -184,50 +164,9 @@ static Parsed device_parse(Plane& pl) {
 // k_part_chunks / k_part_copy over a segment table whose sources lie anywhere in the plane; `bound`: the bytes the destination
 // was sized for (the grid follows it).  Returns the faults; the output in *dst_out.
 static uint64_t device_copy(Plane& pl, const std::vector<uint64_t>& dst_off, const std::vector<uint64_t>& src_pos, uint64_t bound, std::string* dst_out) {
-    using namespace qpart;
-    const uint32_t n = (uint32_t)(dst_off.size() - 1);
-    const uint64_t total = dst_off[n];
-    uint64_t bad = total > bound ? 1 : 0;
-    std::vector<uint8_t> dst_alloc(bound + 2 * PART_SLACK, 0xEE), stored(bound + 2 * PART_SLACK, 0);
-    uint8_t* dst = dst_alloc.data() + PART_SLACK;
-    const auto goff = [&](uint32_t j) { return dst_off[j]; };
-    const uint64_t max_chunks = chunks_of(bound);
-    std::vector<uint32_t> chunk_first(max_chunks + 1, 0xFFFFFFFFu);
-    for (uint64_t c = 0; c < max_chunks; ++c) if (c * PART_CHUNK < total) chunk_first[c] = find_segment(goff, 0u, n, c * PART_CHUNK);
-    const auto load16 = [&](int64_t a) { return pl.load16(a); };
-    for (uint64_t c = 0; c < max_chunks; ++c) {
-        const uint64_t c0 = c * PART_CHUNK;
-        if (c0 >= total) continue;
-        const uint64_t cend = c0 + PART_CHUNK < total ? c0 + PART_CHUNK : total;
-        const uint32_t jf = chunk_first[c];
-        const uint32_t hi = cend < total ? chunk_first[c + 1] + 1u : n;
-        const uint32_t jl = find_segment(goff, jf, hi, cend - 1);
-        const uint32_t m = jl - jf + 1u;
-        const bool in_lds = m <= PART_LDS_SEGS;
-        std::vector<uint64_t> s_off, s_src;
-        if (in_lds) {
-            s_off.resize(PART_LDS_SEGS + 1); s_src.resize(PART_LDS_SEGS);
-            for (uint32_t i = 0; i <= m; ++i) { s_off.at(i) = dst_off[jf + i]; if (i < m) s_src.at(i) = src_pos[jf + i]; }
-        }
-        for (uint32_t tid = 0; tid < PART_THREADS; ++tid)
-            for (uint32_t it = 0; it < PART_VECS_PER_LANE; ++it) {
-                const uint64_t d0 = c0 + ((uint64_t)it * PART_THREADS + tid) * PART_VEC;
-                if (d0 >= cend) break;
-                Vec16 v;
-                if (in_lds) v = gather_vector([&](uint32_t j) { return s_off.at(j); }, [&](uint32_t j) { return s_src.at(j); }, load16, 0u, m, d0, total);
-                else v = gather_vector(goff, [&](uint32_t j) { return src_pos[j]; }, load16, jf, jl + 1u, d0, total);
-                if (d0 + PART_VEC > bound + PART_SLACK) { ++bad; continue; }
-                memcpy(dst + d0, v.w, 16);
-                for (uint32_t i = 0; i < 16; ++i) ++stored[PART_SLACK + d0 + i];
-            }
-    }
-    const uint64_t vec_end = (total + PART_VEC - 1) / PART_VEC * PART_VEC;
-    for (uint64_t i = 0; i < stored.size(); ++i) {
-        const bool inside = i >= PART_SLACK && i < PART_SLACK + vec_end;
-        if (stored[i] != (inside ? 1 : 0)) ++bad;
-    }
-    dst_out->assign(reinterpret_cast<const char*>(dst), total);
-    return bad + pl.stray;
+    const CopyRun r = copy_schedule(dst_off, src_pos, bound, [&](uint32_t, int64_t a) { return pl.load16(a); });
+    dst_out->assign(reinterpret_cast<const char*>(r.out.data()), std::min<size_t>(dst_off.back(), r.out.size()));
+    return r.bad + pl.stray;
 }
 
 // ---- texts -----------------------------------------------------------------------------------------------------------------------
@@ -253,9 +192,9 @@ static std::string join(const std::vector<Read>& reads, bool final_newline) {
 }
 
 // one text through the device schedule against the sequential parser: records, offsets, first bad record, tabs; returns faults
-static uint64_t check_parse(const std::string& t, Parsed* keep = nullptr, Plane** keep_plane = nullptr) {
+static uint64_t check_parse(const std::string& t, Parsed* keep = nullptr, TextPlane** keep_plane = nullptr) {
     const Want w = sequential(t);
-    Plane* pl = new Plane(t);
+    TextPlane* pl = new TextPlane(t);
     Parsed p = device_parse(*pl);
     uint64_t bad = p.faults;
     const uint64_t got_bad = p.bad_line == FQ_NO_LINE ? 0 : p.bad_line / 4 + 1;
@@ -421,7 +360,7 @@ int main(int argc, char** argv) {
             const uint32_t n = k < 8 ? 1 + (uint32_t)k : 20 + (uint32_t)rnd_below(k < 50 ? 80 : 700);
             for (uint32_t i = 0; i < n; ++i) reads.push_back(make_read(i + k, k % 7 == 0 ? 1 + rnd_below(3) : 1 + rnd_below(k % 3 ? 300 : 1500)));
             const std::string t = join(reads, k % 2 == 0);
-            Parsed p; Plane* pl = nullptr;
+            Parsed p; TextPlane* pl = nullptr;
             uint64_t bad = check_parse(t, &p, &pl);
             // bases: segment r = the sequence line of read r
             std::string bases, want_bases;

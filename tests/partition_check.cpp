@@ -14,22 +14,11 @@
 #include <vector>
 
 #include "partition_core.h"
+#include "check_common.h"
 
 using namespace qpart;
 
-static uint64_t g_rng = 1;
-static uint64_t rnd() {                                   // SplitMix64
-    uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint64_t rnd_below(uint64_t n) { return n ? rnd() % n : 0; }
-
 struct Seg { uint64_t gap; uint64_t len; };               // `gap` source bytes that are not kept, then `len` kept bytes
-
-struct Section { const char* name; uint64_t cases = 0, bad = 0; };
-static void report(const Section& s) { printf("%s: %llu cases, %llu mismatches\n", s.name, (unsigned long long)s.cases, (unsigned long long)s.bad); }
 
 // one run of the device schedule over a segment list; returns the number of wrong / doubly stored / stray bytes and loads outside the slack
 static uint64_t run_copy(const std::vector<Seg>& segs, uint64_t tail_gap, uint64_t* lds_chunks = nullptr, uint64_t* global_chunks = nullptr) {
@@ -39,68 +28,22 @@ static uint64_t run_copy(const std::vector<Seg>& segs, uint64_t tail_gap, uint64
     for (uint32_t j = 0; j < n; ++j) { n_src += segs[j].gap; src_pos[j] = n_src; dst_off[j] = total; n_src += segs[j].len; total += segs[j].len; }
     dst_off[n] = total;
     n_src += tail_gap;
-    // the input batch: slack, n_src bases, slack; the output batch: slack, room for the input's bases, slack
-    std::vector<uint8_t> src_alloc(n_src + 2 * PART_SLACK), dst_alloc(n_src + 2 * PART_SLACK, 0xEE), stored(n_src + 2 * PART_SLACK, 0);
-    for (auto& b : src_alloc) b = (uint8_t)rnd();
-    const uint8_t* src = src_alloc.data() + PART_SLACK;
-    uint8_t* dst = dst_alloc.data() + PART_SLACK;
-    uint64_t bad = 0;
-    const auto load16 = [&](int64_t a) {
-        Vec16 v; v.w[0] = v.w[1] = v.w[2] = v.w[3] = 0;
-        if ((a & 15) != 0 || a < -(int64_t)PART_SLACK || a + 16 > (int64_t)(n_src + PART_SLACK)) { ++bad; return v; }
-        memcpy(v.w, src + a, 16);
-        return v;
-    };
-    const auto goff = [&](uint32_t j) { return dst_off[j]; };
-    // k_part_chunks (the grid is sized by the input's bases)
-    const uint64_t max_chunks = chunks_of(n_src);
-    std::vector<uint32_t> chunk_first(max_chunks + 1, 0xFFFFFFFFu);
-    for (uint64_t c = 0; c < max_chunks; ++c) {
-        if (c * PART_CHUNK >= total) continue;
-        chunk_first[c] = find_segment(goff, 0u, n, c * PART_CHUNK);
-    }
-    // k_part_copy
-    for (uint64_t c = 0; c < max_chunks; ++c) {
-        const uint64_t c0 = c * PART_CHUNK;
-        if (c0 >= total) continue;
-        const uint64_t cend = c0 + PART_CHUNK < total ? c0 + PART_CHUNK : total;
-        const uint32_t jf = chunk_first[c];
-        const uint32_t hi = cend < total ? chunk_first[c + 1] + 1u : n;
-        const uint32_t jl = find_segment(goff, jf, hi, cend - 1);
-        if (!(dst_off[jf] <= c0 && dst_off[jf + 1] > c0 && dst_off[jl] <= cend - 1 && dst_off[jl + 1] > cend - 1)) ++bad;
-        const uint32_t m = jl - jf + 1u;
-        const bool in_lds = m <= PART_LDS_SEGS;
-        std::vector<uint64_t> s_off, s_src;                   // (sized like the kernel's arrays: a sanitizer sees an index behind them)
-        if (in_lds) {
-            s_off.resize(PART_LDS_SEGS + 1); s_src.resize(PART_LDS_SEGS);
-            for (uint32_t i = 0; i <= m; ++i) { s_off.at(i) = dst_off[jf + i]; if (i < m) s_src.at(i) = src_pos[jf + i]; }
-            if (lds_chunks) ++*lds_chunks;
-        } else if (global_chunks) ++*global_chunks;
-        for (uint32_t tid = 0; tid < PART_THREADS; ++tid)
-            for (uint32_t it = 0; it < PART_VECS_PER_LANE; ++it) {
-                const uint64_t d0 = c0 + ((uint64_t)it * PART_THREADS + tid) * PART_VEC;
-                if (d0 >= cend) break;
-                Vec16 v;
-                if (in_lds)
-                    v = gather_vector([&](uint32_t j) { return s_off.at(j); }, [&](uint32_t j) { return s_src.at(j); }, load16, 0u, m, d0, total);
-                else
-                    v = gather_vector(goff, [&](uint32_t j) { return src_pos[j]; }, load16, jf, jl + 1u, d0, total);
-                if (d0 + PART_VEC > n_src + PART_SLACK) { ++bad; continue; }             // a store behind the allocation
-                memcpy(dst + d0, v.w, 16);
-                for (uint32_t i = 0; i < 16; ++i) ++stored[PART_SLACK + d0 + i];
-            }
-    }
-    // every byte of the output's vectors stored once, nothing else touched, the bytes are the concatenation
-    const uint64_t vec_end = (total + PART_VEC - 1) / PART_VEC * PART_VEC;
-    for (uint64_t i = 0; i < stored.size(); ++i) {
-        const bool inside = i >= PART_SLACK && i < PART_SLACK + vec_end;
-        if (stored[i] != (inside ? 1 : 0)) ++bad;
-        if (!inside && dst_alloc[i] != 0xEE) ++bad;
-    }
+    // the input batch: slack, n_src bases, slack; the output batch: slack, room for the input's bases, slack (the grid is sized by
+    // the input's bases)
+    std::vector<uint8_t> payload(n_src);
+    for (auto& b : payload) b = (uint8_t)rnd();
+    Plane in(payload);
+    const uint8_t* src = payload.data();
+    const CopyRun r = copy_schedule(dst_off, src_pos, n_src, [&](uint32_t, int64_t a) { return in.load16(a); });
+    if (lds_chunks) *lds_chunks += r.lds_chunks;
+    if (global_chunks) *global_chunks += r.global_chunks;
+    uint64_t bad = r.bad + in.stray;
+    // the bytes are the concatenation
+    const uint8_t* dst = r.out.data();
     uint64_t d = 0;
     for (uint32_t j = 0; j < n; ++j)
         for (uint64_t i = 0; i < segs[j].len; ++i, ++d) if (dst[d] != src[src_pos[j] + i]) ++bad;
-    for (; d < vec_end; ++d) if (dst[d] != 0) ++bad;             // (the last vector's bytes behind the total are zeros)
+    for (; d < r.out.size(); ++d) if (dst[d] != 0) ++bad;        // (the last vector's bytes behind the total are zeros)
     return bad;
 }
 

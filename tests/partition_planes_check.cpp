@@ -16,23 +16,13 @@
 #include <vector>
 
 #include "partition_core.h"
+#include "check_common.h"
 
 using namespace qpart;
 
-static uint64_t g_rng = 1;
-static uint64_t rnd() {                                   // SplitMix64
-    uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint64_t rnd_below(uint64_t n) { return n ? rnd() % n : 0; }
 static uint8_t permuted(uint8_t x) { return (uint8_t)(x * 167u + 13u); }       // (167 is odd: a permutation of 0..255 without a fixed byte pattern)
 
 struct Seg { uint64_t gap; uint64_t len; };               // `gap` source bytes that are not kept, then `len` kept bytes
-
-struct Section { const char* name; uint64_t cases = 0, bad = 0; };
-static void report(const Section& s) { printf("%s: %llu cases, %llu mismatches\n", s.name, (unsigned long long)s.cases, (unsigned long long)s.bad); }
 
 // one run of the device schedule over a segment list with two planes; returns the number of wrong / doubly stored / stray bytes,
 // loads outside the slack and vectors on which the one-plane form of gather_vectors differs from gather_vector

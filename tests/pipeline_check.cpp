@@ -15,20 +15,9 @@
 #include <vector>
 
 #include "pipeline_core.h"
+#include "check_common.h"
 
 using qk::HostPool;
-
-static uint64_t g_rng = 1;
-static uint64_t rnd() {                                   // SplitMix64
-    uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint64_t rnd_below(uint64_t n) { return n ? rnd() % n : 0; }
-
-struct Section { const char* name; uint64_t cases = 0, bad = 0; };
-static void report(const Section& s) { printf("%s: %llu cases, %llu mismatches\n", s.name, (unsigned long long)s.cases, (unsigned long long)s.bad); }
 
 static const unsigned WORKERS[] = {0u, 1u, 2u, 7u};
 

@@ -23,7 +23,7 @@ SECTIONS = {"masks": 4000 * 5, "newlines at block edges": 4 * 4 * 4 * 2 * 2, "sh
 def _build(tmp_path_factory, name, extra):
     exe = str(tmp_path_factory.mktemp(name) / "fqtext_check")
     subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Werror"] + extra +
-                          ["-I", CSRC, os.path.join(ROOT, "tests", "fqtext_check.cpp"), "-o", exe])
+                          ["-I", CSRC, "-I", os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "fqtext_check.cpp"), "-o", exe])
     return exe
 
 
@@ -69,9 +69,17 @@ def test_the_check_and_the_kernels_share_their_arithmetic():
     for name in ("qfq::blocks_of", "qfq::lines_of", "qfq::records_of", "qfq::output_bound", "qfq::fq_constants", "qfq::FQ_CONST_BYTES",
                  "qfq::FQ_NO_LINE", "k_part_copy<1>", "k_part_chunks", "part_scan_launch<uint64_t>", "part_keys", "part_order"):
         assert name in host, name
+    # the argument check, the tail and the read-out of the demultiplexed text are the text products' shared layer, which launches
+    # nothing and keeps off the partition's scratch
+    with open(os.path.join(CSRC, "text_out_host.inc")) as fh:
+        shared = fh.read()
+    for name in ("batch_call_check", "text_out_finish", "text_out_fetch_check", "text_out_fetch_copies", "text_out_devptr"):
+        assert "static " in shared and name + "(" in shared and name + "(" in host, name
+    assert "hipLaunchKernelGGL" not in shared and "part_keys" not in shared and "c->batch.part" not in shared
     with open(os.path.join(CSRC, "qcat_hip.hip")) as fh:
         unit = fh.read()
     assert '#include "kernels_fqtext.inc"' in unit and '#include "fqtext_host.inc"' in unit
+    assert unit.index('#include "batch_host.inc"') < unit.index('#include "text_out_host.inc"') < unit.index('#include "fqtext_host.inc"')
     with open(os.path.join(CSRC, "fqtext_core.h")) as fh:
         core = fh.read()
     assert "constexpr uint32_t FQ_BLOCK = FQ_ROUND * FQ_ROUNDS;" in core and '#include "partition_core.h"' in core

@@ -20,7 +20,7 @@ SECTIONS = {"primitives": 16 + 136 + 4 * 8 * 8 * 2 + 9, "residues": 16 * 16 * 10
 def _build(tmp_path_factory, name, extra):
     exe = str(tmp_path_factory.mktemp(name) / "partition_check")
     subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Werror"] + extra +
-                          ["-I", os.path.join(ROOT, "qcat_amd", "csrc"), os.path.join(ROOT, "tests", "partition_check.cpp"), "-o", exe])
+                          ["-I", os.path.join(ROOT, "qcat_amd", "csrc"), "-I", os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "partition_check.cpp"), "-o", exe])
     return exe
 
 

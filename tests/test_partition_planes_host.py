@@ -26,7 +26,7 @@ NEW_SYMBOLS = ["qcat_batch_upload_fastq", "qcat_batch_has_qualities", "qcat_batc
 def _build(tmp_path_factory, name, extra):
     exe = str(tmp_path_factory.mktemp(name) / "partition_planes_check")
     subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Werror"] + extra +
-                          ["-I", os.path.join(ROOT, "qcat_amd", "csrc"), os.path.join(ROOT, "tests", "partition_planes_check.cpp"), "-o", exe])
+                          ["-I", os.path.join(ROOT, "qcat_amd", "csrc"), "-I", os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "partition_planes_check.cpp"), "-o", exe])
     return exe
 
 

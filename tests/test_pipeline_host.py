@@ -30,7 +30,7 @@ BUILDS = {"plain": [],
 def pipeline_check(request, tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("pipeline_" + request.param) / "pipeline_check")
     subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Werror", "-pthread"] + BUILDS[request.param] +
-                          ["-I", os.path.join(ROOT, "qcat_amd", "csrc"), os.path.join(ROOT, "tests", "pipeline_check.cpp"), "-o", exe])
+                          ["-I", os.path.join(ROOT, "qcat_amd", "csrc"), "-I", os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "pipeline_check.cpp"), "-o", exe])
     return request.param, exe
 
 

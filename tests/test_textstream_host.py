@@ -23,7 +23,7 @@ SECTIONS = {"fasta shapes": 2 * (41 + 2), "fasta refusals": 14 * 3 * 2 * 2 - 2 *
 def _build(tmp_path_factory, name, extra):
     exe = str(tmp_path_factory.mktemp(name) / "textstream_check")
     subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Werror"] + extra +
-                          ["-I", CSRC, os.path.join(ROOT, "tests", "textstream_check.cpp"), "-o", exe])
+                          ["-I", CSRC, "-I", os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "textstream_check.cpp"), "-o", exe])
     return exe
 
 
@@ -72,9 +72,15 @@ def test_the_check_and_the_kernels_share_their_arithmetic():
     with open(os.path.join(CSRC, "textstream_host.inc")) as fh:
         host = fh.read()
     for name in ("qann::ANNOT_SEGS", "qann::output_bound", "qann::tag_const_off", "qann::tag_plane_bytes", "qann::annot_constants",
-                 "qtsv::tables_build", "k_annot_segments", "k_annot_firsts", "k_annot_copy", "k_part_chunks", "part_scan_launch<uint64_t>"):
+                 "k_annot_segments", "k_annot_firsts", "k_annot_copy", "k_part_chunks", "part_scan_launch<uint64_t>"):
         assert name in host, name
     assert "k_part_copy" not in host and "part_keys" not in host             # (scratch and copy of its own, no sort)
+    # the id slots of the tag plane: the text products' shared layer builds them, this file calls it
+    with open(os.path.join(CSRC, "text_out_host.inc")) as fh:
+        shared = fh.read()
+    for name, caller in (("qtsv::tables_build", "name_tables_build("), ("qtsv::TSV_MAX_DEN", "tables_at(")):
+        assert name in shared and name not in host and caller in shared and caller in host, name
+    assert "hipLaunchKernelGGL" not in shared and "part_keys" not in shared and "c->batch.part" not in shared and "k_part_copy" not in shared
     with open(os.path.join(CSRC, "kernels_partition.inc")) as fh:
         part = fh.read()
     assert "k_annot" not in part and "ANNOT_TAG" not in part                  # (k_part_copy<1> / <2> stay what they are)

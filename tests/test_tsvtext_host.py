@@ -22,7 +22,7 @@ SECTIONS = {"decimal": 2 + 9 * 3 * 3 + 5 + 2000 * 2, "titles": 3 * 6 * 2 * 2, "r
 def _build(tmp_path_factory, name, extra):
     exe = str(tmp_path_factory.mktemp(name) / "tsvtext_check")
     subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Werror"] + extra +
-                          ["-I", CSRC, os.path.join(ROOT, "tests", "tsvtext_check.cpp"), "-o", exe])
+                          ["-I", CSRC, "-I", os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "tsvtext_check.cpp"), "-o", exe])
     return exe
 
 
@@ -83,10 +83,16 @@ def test_the_check_and_the_kernels_share_their_arithmetic():
     assert not re.search(r"'\\t'|'\\n'|/ ?10|% ?10|none|None", re.sub(r"//.*", "", text))     # (separators, digits and constants live in the header)
     with open(os.path.join(CSRC, "tsvtext_host.inc")) as fh:
         host = fh.read()
-    for name in ("qtsv::score_table_build", "qtsv::tables_build", "qtsv::output_bound", "qtsv::title_bound", "qtsv::tiles_of",
-                 "qtsv::TSV_MAX_DEN", "qtsv::TSV_THREADS", "fq_repr_double", "part_scan_launch<uint64_t>", "k_tsv_lengths", "k_tsv_tiles",
+    for name in ("qtsv::score_table_build", "qtsv::output_bound", "qtsv::title_bound", "qtsv::tiles_of",
+                 "qtsv::TSV_THREADS", "fq_repr_double", "part_scan_launch<uint64_t>", "k_tsv_lengths", "k_tsv_tiles",
                  "k_tsv_write"):
         assert name in host, name
+    # the blob and its pointers on the device: the text products' shared layer builds them, this file calls it
+    with open(os.path.join(CSRC, "text_out_host.inc")) as fh:
+        shared = fh.read()
+    for name, caller in (("qtsv::tables_build", "name_tables_build("), ("qtsv::TSV_MAX_DEN", "tables_at(")):
+        assert name in shared and name not in host and "static " in shared and caller in shared and caller in host, name
+    assert "hipLaunchKernelGGL" not in shared and "part_keys" not in shared and "c->batch.part" not in shared
     assert "part_keys" not in host and "c->batch.part" not in host                           # (scratch of its own, not the partition's)
     with open(os.path.join(CSRC, "qcat_hip.hip")) as fh:
         unit = fh.read()

@@ -16,21 +16,11 @@
 #include <vector>
 
 #include "upload_core.h"
+#include "check_common.h"
 
 using namespace qupload;
 
-static uint64_t g_rng = 1;
-static uint64_t rnd() {                                   // SplitMix64
-    uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static uint64_t rnd_below(uint64_t n) { return n ? rnd() % n : 0; }
 static bool differs(const uint8_t* a, const uint8_t* b, uint64_t n) { return n && memcmp(a, b, (size_t)n) != 0; }      // (n = 0: the pointers may be null)
-
-struct Section { const char* name; uint64_t cases = 0, bad = 0; };
-static void report(const Section& s) { printf("%s: %llu cases, %llu mismatches\n", s.name, (unsigned long long)s.cases, (unsigned long long)s.bad); }
 
 // a batch in both input forms: the concatenated bases with their offsets, and a copy of every read in an allocation of its own
 // (exactly its length, so that a byte read past a read's end is the address sanitizer's; an empty read has a null pointer)
