@@ -596,6 +596,48 @@ int  qcat_ctx_fetch_annot_text(qcat_ctx* ctx, uint8_t* text, uint64_t cap, uint6
 /* the stream in device memory (owned by ctx until its next qcat_batch_annot_text), for callers that stay in HBM */
 void* qcat_ctx_annot_text_devptr(qcat_ctx* ctx);
 
+/* ---- the evaluation of a text batch in device memory: qcat-eval's classes and summary, qcat-roc's table ----
+ * The reference judges a demultiplexer by `truebc=<ids>` in every read's comment (qcat/eval.py over the rows of --tsv, qcat/eval_roc.py
+ * over the listing eval.py prints).  This call gives both answers for a text batch by the calls of `records` (as in
+ * qcat_batch_tsv_text: NULL = this context's latest resident scan of these reads with `kit`), from the titles, the records and the
+ * id tables in device memory.  The reads evaluated are the reads that have a TSV row: every read the kit's min_read_length keeps (the
+ * partition's rule); a dropped read is in no count.  Per evaluated read:
+ *   call text bc   what the TSV's barcode column prints: str(Barcode.id) from `names`, id "/" id2 in dual mode, "none" for a read
+ *                  that is not called ("called" as in qcat_batch_tsv_text)
+ *   comment        the bytes behind the stored title's first blank (the text plane holds tabs as blanks)
+ *   truth          the comment split at every single blank; a token counts when it holds exactly one '=' -- key the bytes in front,
+ *                  value the bytes behind, which may be empty --; the LAST counting token whose key is exactly "truebc" gives the
+ *                  value V, and truebc = V.split(",")
+ *   eval class     CORRECT when bc equals an element of the list ("none" against "none" included), otherwise FN when bc is "none",
+ *                  otherwise FP when V == "none", otherwise INCORRECT; total = correct + incorrect + fn + fp
+ *   ROC            at threshold q in 0 .. 1000 the call is "none" when score < q / 10.0.  Without a call: true_negative when
+ *                  V == "none", else false_negative.  With a call: false_positive when V == "none", else correct when bc equals the
+ *                  WHOLE of V (the reference compares with a list of one, so a comma list never matches), else incorrect.
+ *   thresholds     compared in integers: a called read survives exactly the q with q * score_den <= raw_score * 1000; its bucket is
+ *                  min(1001, raw_score * 1000 / score_den + 1), the bucket of a read without a call is 0 (the same verdict as the
+ *                  doubles' score < q / 10.0 for every score a kit can write)
+ * A read the reference's reader fails on makes the call fail: QCAT_ERR_ARG with the 1-based number of the FIRST such read in the
+ * message (a minimum the device keeps, read at the call's one synchronisation), no result is left behind, the context stays usable:
+ * a kept read without a truebc token, with an empty name, or with a name that begins with "name"; a called record with
+ * score_den < 1 or raw_score < 0.
+ * flags = QCAT_EVAL_FROM_COMMENT: the reference's `qcat-eval reads.fastq` for the annotated stream (qcat_batch_annot_text): bc is
+ * the value of the last counting "barcode" token ("none" when that value is empty), the score is -1 (bucket 0), every read of the
+ * batch is evaluated, and `kit`, `records` and `names` are not looked at (they may be NULL); refused as above: a read without
+ * truebc or without barcode.  Other flag bits are reserved and must be 0.
+ * QCAT_ERR_ARG before anything is enqueued: a batch without a text plane, NULL `names` or a NULL id table in it, records == NULL
+ * without a matching scan.  Uses scratch of its own: a context keeps its demultiplexed text, its TSV text, its stream and its
+ * evaluation side by side.  Enqueues on the context's stream, synchronises once.  Integer adds only: the same bytes run after run. */
+enum { QCAT_EVAL_FROM_COMMENT = 1 };
+typedef struct qcat_eval_counts { int64_t total, correct, incorrect, fn, fp; } qcat_eval_counts;
+int  qcat_batch_eval(qcat_ctx* ctx, const qcat_kit* kit, const qcat_batch* batch, const qcat_result* records,
+                     const qcat_tsv_names* names, uint32_t flags, qcat_eval_counts* out);
+/* the latest evaluation of this context, one entry per read of the batch: cls (0 dropped, 1 CORRECT, 2 INCORRECT, 3 FN, 4 FP),
+ * kind (0 truth none, 1 bc equals the whole value, 2 other), bucket; and roc, 1001 rows of six: total, correct, incorrect,
+ * true_negative, false_negative, false_positive at q = 0 .. 1000.  Any of the four may be NULL.  Every qcat_batch_eval drops the
+ * evaluation the context held before it works: after a call that failed -- a refused read included -- there is none to fetch
+ * (QCAT_ERR_ARG), an earlier one is not kept. */
+int  qcat_ctx_fetch_eval(qcat_ctx* ctx, uint8_t* cls, uint8_t* kind, uint16_t* bucket, int64_t* roc /* 1001 * 6 */);
+
 /* the latest partition of this context: bin b = reads [bin_first[b], bin_first[b+1]) of `out`
  * (n_bins + 1 entries); source[i] = index in the input batch of read i of `out` (n_reads entries, may be NULL) */
 int  qcat_ctx_fetch_partition(qcat_ctx* ctx, uint64_t* bin_first, int32_t n_bins, uint32_t* source);

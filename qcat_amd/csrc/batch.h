@@ -1,7 +1,7 @@
 // batch.h -- the resident batch (reads in device memory) and what belongs to it on the host (host only, like dev_buf.h): the
 // type behind qcat_batch*, its two makers' building blocks -- an owned batch allocates its planes, a view borrows a context's
 // staging -- the guard of a batch under construction, and the scratch of the calls over a batch: the partition, the filter, the
-// text parse and the three text products (their shared types: text_out.h).  The functions are in batch_host.inc and the host
+// text parse, the three text products (their shared types: text_out.h) and the evaluation.  The functions are in batch_host.inc and the host
 // files named at each scratch.  Included by qcat_hip.hip in front of middle_host.inc.
 #pragma once
 #include <memory>
@@ -117,6 +117,18 @@ struct AnnotScratch {
     MirroredTable tags;
     TextOut text;
 };
+// the evaluation of a text batch (kernels_eval.inc, eval_host.inc), scratch of its own beside the three texts: the planes, the
+// counts and the ROC table of the latest qcat_batch_eval (valid: a failed call leaves none behind); the id slots' blob on the
+// device beside its host copy
+struct EvalScratch {
+    qk::DevBuf<uint8_t> cls, kind;
+    qk::DevBuf<uint16_t> bucket;
+    qk::DevBuf<uint32_t> hist, bad;
+    qk::DevBuf<int64_t> roc;
+    MirroredTable tables;
+    uint32_t n_reads = 0;
+    bool valid = false;
+};
 // what a context keeps for the batch functions
 struct BatchScratch {
     PartScratch part;
@@ -124,6 +136,7 @@ struct BatchScratch {
     FqTextScratch fqtext;
     TsvScratch tsv;
     AnnotScratch annot;
+    EvalScratch eval;
     qk::DevBuf<qcat_result> recs;              // records a caller handed over, of whichever call runs (records_on_device, text_out_host.inc)
     qk::DevBuf<uint32_t> offs_bad;             // qcat_batch_from_device: the flag of k_offsets_check
 };

@@ -60,6 +60,7 @@
     X(AUTO_WORKERS, "contexts of the kit-auto file loop") \
     X(RESIDENT_AUTO_CHUNK, "reads per adapter pass of a resident kit-auto scan, cut at whole vote batches (default 1048576, the file loop's)") \
     X(FILTER_TABLE_BYTES, "bytes of the key counters of --filter-barcodes on the device: the batches are filtered in rounds that fit (default 67108864; at least one batch per round)") \
+    X(EVAL_SHAPE, "0 / 1: the classify pass of qcat_batch_eval with one lane / a group of eight lanes per read (default 0)") \
     X(NO_GRAPH, "1: host-buffer calls never replay a captured graph") \
     X(DEBUG_VOTE, "1: print the kit vote") \
     X(DEBUG_BINS, "1: print the jobs per length class") \

@@ -41,6 +41,7 @@
 #include "kernels_fqtext.inc"
 #include "kernels_tsvtext.inc"
 #include "kernels_textstream.inc"
+#include "kernels_eval.inc"
 #include "kernels_filter.inc"
 #include "static_registry.inc"
 #include "pipeline.h"
@@ -1266,6 +1267,8 @@ extern "C" int qcat_sg_align(qcat_ctx* c, const uint8_t* queries, const uint64_t
 #include "tsvtext_host.inc"
 // the driver's annotated single stream of a scanned text batch (the id texts: the id slots of the TSV tables)
 #include "textstream_host.inc"
+// the evaluation of a scanned text batch: qcat-eval's classes and summary, qcat-roc's table (the id texts: the id slots again)
+#include "eval_host.inc"
 
 // ------------------------------------------------------------------------------------------
 // multi-GPU count reduction (RCCL)

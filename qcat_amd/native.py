@@ -112,6 +112,11 @@ class TsvNamesStruct(C.Structure):
     _fields_ = [("kit_name", C.POINTER(C.c_char_p)), ("bc_id", C.POINTER(C.POINTER(C.c_int32))), ("bc2_id", C.POINTER(C.POINTER(C.c_int32)))]
 
 
+class EvalCounts(C.Structure):
+    """qcat_eval_counts (include/qcat_hip.h)"""
+    _fields_ = [("total", C.c_int64), ("correct", C.c_int64), ("incorrect", C.c_int64), ("fn", C.c_int64), ("fp", C.c_int64)]
+
+
 class TsvNames(object):
     """What the TSV rows of :meth:`NativeContext.tsv_text` print besides the bytes of the text: a ``qcat_tsv_names`` and the
     buffers it points to, from the AdapterLayout list of the kit -- the kit's name (``None`` for a layout without one: simple
@@ -444,6 +449,8 @@ class HipLibrary(object):
             "qcat_batch_annot_text": (C.c_int, [vp, vp, vp, vp, C.POINTER(TsvNamesStruct), u32, C.POINTER(C.c_uint64)]),
             "qcat_ctx_fetch_annot_text": (C.c_int, [vp, vp, C.c_uint64, vp]),
             "qcat_ctx_annot_text_devptr": (vp, [vp]),
+            "qcat_batch_eval": (C.c_int, [vp, vp, vp, vp, C.POINTER(TsvNamesStruct), u32, C.POINTER(EvalCounts)]),
+            "qcat_ctx_fetch_eval": (C.c_int, [vp, vp, vp, vp, vp]),
             "qcat_ctx_partition_bins_devptr": (vp, [vp]),
             "qcat_ctx_partition_source_devptr": (vp, [vp]),
             "qcat_ctx_last_timing": (C.c_int, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
@@ -859,6 +866,21 @@ class AnnotText(object):
         self.text, self.rec_first = text, rec_first
 
 
+EVAL_FROM_COMMENT = 1                  # qcat_batch_eval: QCAT_EVAL_FROM_COMMENT
+EVAL_CLASSES = ("", "CORRECT", "INCORRECT", "FN", "FP")      # the class byte of a read (0: dropped) as qcat-eval prints it
+ROC_COLUMNS = ("total", "correct", "incorrect", "true_negative", "false_negative", "false_positive")
+
+
+class EvalText(object):
+    """What :meth:`NativeContext.eval_text` returns: ``counts`` (dict: total, correct, incorrect, fn, fp -- the summary of
+    qcat-eval), ``classes`` (uint8 per read: 0 dropped, 1 CORRECT, 2 INCORRECT, 3 FN, 4 FP), ``kinds`` (uint8 per read: 0 truth
+    none, 1 the call equals the whole truebc value, 2 other), ``buckets`` (uint16 per read: the call stands at the thresholds
+    q < bucket) and ``roc`` (int64, 1001 x 6: :data:`ROC_COLUMNS` at the score thresholds q / 10.0 of qcat-roc)."""
+
+    def __init__(self, counts, classes, kinds, buckets, roc):
+        self.counts, self.classes, self.kinds, self.buckets, self.roc = counts, classes, kinds, buckets, roc
+
+
 class NativeContext(object):
     """``qcat_ctx*`` handle: one device, one stream; not re-entrant."""
 
@@ -1001,6 +1023,25 @@ class NativeContext(object):
                                                           C.byref(names.struct) if names is not None else None, 0, C.byref(total)))
         text, rec_first = self._fetch_text(total, batch.n_reads, lambda t, cap, first: self.hip.lib.qcat_ctx_fetch_annot_text(self.handle, t, cap, first))
         return AnnotText(text.tobytes(), rec_first)
+
+    def eval_text(self, kit, batch, names, records=None, from_comment=False):
+        """qcat_batch_eval of a batch made by :meth:`ResidentBatch.upload_text`: the reference's qcat-eval classes and summary
+        and qcat-roc's table by the ``truebc=`` of every title, counted on the device -- an :class:`EvalText`.  ``names`` and
+        ``records`` as in :meth:`tsv_text`; ``from_comment``: the calls are the ``barcode=`` of the titles themselves
+        (``qcat-eval reads.fastq``), and ``kit``, ``names`` and ``records`` are not looked at."""
+        counts = EvalCounts()
+        if from_comment:
+            self.hip.check(self.hip.lib.qcat_batch_eval(self.handle, None, batch.handle, None, None, EVAL_FROM_COMMENT, C.byref(counts)))
+        else:
+            handle, recs = self._kit_and_records("eval_text", kit, batch, records)
+            self.hip.check(self.hip.lib.qcat_batch_eval(self.handle, handle, batch.handle, recs,
+                                                        C.byref(names.struct) if names is not None else None, 0, C.byref(counts)))
+        n = batch.n_reads
+        classes, kinds = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        buckets = np.zeros(n, dtype=np.uint16)
+        roc = np.zeros((1001, len(ROC_COLUMNS)), dtype=np.int64)
+        self.hip.check(self.hip.lib.qcat_ctx_fetch_eval(self.handle, classes.ctypes.data, kinds.ctypes.data, buckets.ctypes.data, roc.ctypes.data))
+        return EvalText({k: int(getattr(counts, k)) for k, _t in EvalCounts._fields_}, classes, kinds, buckets, roc)
 
     def detect_kit(self, kit, bases, offsets):
         """per-template (votes, first voting read) of qcat_detect_kit."""

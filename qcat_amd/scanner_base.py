@@ -533,6 +533,17 @@ class BarcodeScanner(object):
             out = ctx.annot_text(kit, batch, self._tsv_names())
         return out.text
 
+    def eval_fastx_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None, tsv=False):
+        """The reference's ``qcat --tsv ... | qcat-eval --tsv -`` and ``| qcat-roc`` for FASTQ or FASTA text whose titles carry
+        ``truebc=<ids>``: one upload, one scan like :meth:`tsv_fastx_text`, one evaluation on the device (qcat_batch_eval) -- a
+        :class:`native.EvalText` with the summary counts, the eval class, ROC kind and score bucket of every read and the
+        1001 x 6 table of qcat-roc.  No row is formatted and no title is parsed here.  ``tsv=True``: ``(evaluation, table)`` with
+        the bytes of :meth:`tsv_fastx_text` from the same upload and scan (qcat-eval's per-read listing prints its columns)."""
+        with self._scanned_text(native.ResidentBatch.upload_text, text, batch_size, trim, min_read_length, qcat_config) as (ctx, kit, batch):
+            out = ctx.eval_text(kit, batch, self._tsv_names())
+            rows = ctx.tsv_text(kit, batch, self._tsv_names()) if tsv else None
+        return (out, self.TSV_HEADER + rows.text) if tsv else out
+
     def demux_fastq_text(self, text, batch_size=4000, trim=False, min_read_length=0, qcat_config=None, tsv=False):
         """:meth:`demux_batches` from FASTQ text to FASTQ text: the bytes of a plain four-line FASTQ file go up, are parsed on the
         device (qcat_batch_upload_fastq_text), scanned like :meth:`demux_batches` scans, and the bytes of every per-barcode
